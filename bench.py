@@ -4,13 +4,17 @@ feature extraction + linear depth-probe train step (DepthHead linear k=1 bindept
 upsample -> DepthLoss -> backward -> AdamW -> LambdaLR) on 224x224 synthetic batches.
 
     python bench.py --gpus N --steps K --warmup W      (N>1: launched by torch.distributed.run)
+    python bench.py ... --full                          (every leg below as well)
+    python bench.py ... --dump-outputs DIR              (what the last timed step computed, as DIR/<name>.npy)
 
 One "step" = the train_depth.py:99-143 loop body over one per-GPU batch already resident in
-HBM.  Rank 0 prints ONE JSON line (contract in the task statement) carrying, besides the
-throughput, a `roofline` object for the dominant kernel (the split-bf16 MFMA GEMM; algorithmic
-2*M*N*K flops per launch / HIP-event duration on the launch stream) and a `cpu_baseline`
-object (the CPU oracle — a port of the reference path — timed on the host cores on a bounded
-sample of the same workload).
+HBM.  Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms
+up, times K steps and reports the throughput and `ms_per_step`, nothing else.  With `--full` the
+line also carries the in-run pipelined-vs-serial check, the serial / sustained / bf16x3 legs, a
+`roofline` object for the dominant kernel (the split-bf16 MFMA GEMM; algorithmic 2*M*N*K flops
+per launch / HIP-event duration on the launch stream, rocprofv3 PMC child passes) and a
+`cpu_baseline` object (the CPU oracle — a port of the reference path — timed on the host cores on
+a bounded sample of the same workload); `--h2d` adds the PCIe-inclusive leg to a `--full` run.
 """
 from __future__ import annotations
 
@@ -157,6 +161,12 @@ def parse_args():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic / mfma_busy then come from the committed profiles/)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the headline: in-run pipeline check, serial / sustained / bf16x3 legs, roofline with live PMC passes, CPU baselines "
+                         "(a plain run only sets up, warms up and times --steps steps; the --no-* / --sustained-steps / --cpu-steps / --h2d options shape these legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): its loss, the probe's parameters after its "
+                         "update, the frozen features it consumed (a fixed, seeded sample of an array past its share of 64 MB)")
     ap.add_argument("--sustained-steps", type=int, default=300, help="extra untimed-by-the-contract leg: the same step for this many more iterations (steady-state clocks); 0 = skip")
     ap.add_argument("--inflight", type=int, default=None,
                     help="frozen-backbone forwards kept in flight on side HIP streams (mvp/pipeline.py); 1 = one serial kernel chain; "
@@ -227,6 +237,30 @@ def self_launch(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def dump_outputs(out_dir, arrays, budget=64_000_000):
+    """Write ``{name: tensor}`` as out_dir/<name>.npy in float32 (float64 stays float64), at most ``budget`` bytes in all: the
+    smallest arrays first, each whole if it fits its even share of what is left, else a fixed sample of its flattened elements
+    (an evenly strided subset from a seeded offset: the same elements in every run of the same shapes)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left, sampled = budget - 4096 * len(items), []  # (room for the .npy headers)
+    for i, (name, t) in enumerate(items):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        cap = (left // (len(items) - i)) // a.itemsize
+        if a.size > cap:
+            stride = -(-a.size // cap)
+            off = int(np.random.default_rng(0).integers(stride))
+            a = np.ascontiguousarray(a.reshape(-1)[off::stride][:cap])
+            sampled.append(f"{name} {list(t.shape)} -> {a.size} elements")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+    if sampled:
+        print("[bench] --dump-outputs sampled: " + "; ".join(sampled), file=sys.stderr)
+
+
 def _gemm_tiles_label(pipe, tiles_shared, B, H, W):
     """Which kernel family the backbone GEMMs of a forward run on (the mirror of pp_takes() in csrc/gemm.hip, mvp.ops.gemm_tile)."""
     from mvp import ops
@@ -243,6 +277,12 @@ def _gemm_tiles_label(pipe, tiles_shared, B, H, W):
 def main():
     args = parse_args()
     warnings.simplefilter("ignore")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.h2d and not args.full:
+        raise SystemExit("--h2d is a leg of the full benchmark: add --full")
+    if not args.full:  # a plain run: the headline's timed steps and nothing else
+        args.sustained_steps, args.no_cpu_baseline, args.no_roofline, args.no_live_pmc, args.no_serial_leg, args.no_alt_precision = 0, True, True, True, True, True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     if args.pmc_child:  # the profiled child: a few steps of the workload, nothing else (steps are set once the group size is known)
@@ -349,11 +389,11 @@ def main():
 
     from mvp.pipeline import pipelined_features
 
-    def run_steps(i0, n, out=None, pipe=pipe, objs=None, model=model):
+    def run_steps(i0, n, out=None, pipe=pipe, objs=None, model=model, last=None):
         """Steps i0 .. i0+n-1, every one the full train_depth.py:99-143 body.  The frozen forwards of upcoming batches (stacked ``group``
         at a time) are in flight on side streams while the probe steps run in order on this stream; the pipeline starts empty and ends
         empty, so all the work of these n steps (the forwards of n batches, n probe forward/backward/AdamW) lies between the caller's two
-        barriers."""
+        barriers.  ``last``: a dict that receives the features the last step consumed (the pipeline's buffers: valid until its next forward)."""
         seq = [batches[i % n_distinct] for i in range(i0, i0 + n)]
         pr_, op_, sc_ = objs if objs is not None else (probe, opt, sched)
         ctx = shared_tiles(True) if (pipe.depth == 1 and force_shared) else contextlib.nullcontext()  # (a pipelined forward selects its policy itself)
@@ -362,6 +402,8 @@ def main():
                 loss = train_depth_step(model, pr_, op_, sc_, loss_fn, None, target, feats=feats)
                 if out is not None:
                     out.append(loss)
+                if last is not None:
+                    last["feats"] = feats
 
     def barrier():
         opt.finish_pending()  # the last step's update belongs to the timed region
@@ -369,19 +411,21 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # ---------------- in-run check (VERDICT r2 #2c): from identical probe / optimizer states, the pipelined loop (grouped forwards, graph
-    # replay) and the one-batch-at-a-time serial loop produce the same per-step losses, bit for bit.  (Also sets the pipeline's graphs up.)
+    # ---------------- the pipeline's graphs set up outside the timed region (one full group + a ragged one, on a throwaway probe), and,
+    # with --full, the in-run check (VERDICT r2 #2c): from identical probe / optimizer states, the pipelined loop (grouped forwards, graph
+    # replay) and the one-batch-at-a-time serial loop produce the same per-step losses, bit for bit.
     pipeline_check = None
     if pipe.depth > 1 and not args.pmc_child and world == 1:
         nchk = pipe.group + min(2, pipe.group)  # one full group + a ragged one
         la, lb = [], []
         run_steps(0, nchk, la, pipe, make_probe())
         torch.cuda.synchronize()
-        run_steps(0, nchk, lb, FeaturePipeline(model, 1), make_probe())
-        torch.cuda.synchronize()
-        same = bool(torch.equal(torch.stack(la), torch.stack(lb)))
-        pipeline_check = {"steps": nchk, "losses_bit_identical_to_serial_loop": same}
-        assert same, "the pipelined loop's losses differ from the serial loop's"
+        if args.full:
+            run_steps(0, nchk, lb, FeaturePipeline(model, 1), make_probe())
+            torch.cuda.synchronize()
+            same = bool(torch.equal(torch.stack(la), torch.stack(lb)))
+            pipeline_check = {"steps": nchk, "losses_bit_identical_to_serial_loop": same}
+            assert same, "the pipelined loop's losses differ from the serial loop's"
 
     from mvp.pipeline import freeze_gc
 
@@ -389,14 +433,20 @@ def main():
     losses = []  # device scalars, reduced after the timed region (no accumulate kernel inside it, no host sync per step)
     run_steps(0, args.warmup, losses)
     barrier()
+    last = {}
     t0 = time.perf_counter()
-    run_steps(args.warmup, args.steps, losses)
+    run_steps(args.warmup, args.steps, losses, last=last)
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:  # before any other leg steps the probe on or reuses the pipeline's buffers
+        outputs = {"loss": losses[-1].reshape(1)}
+        outputs.update({f"probe.{n}": p for n, p in probe.named_parameters()})
+        outputs.update({f"features.tap{j}": t for j, t in enumerate(last["feats"])})
+        dump_outputs(args.dump_outputs, outputs)
     last_loss = float(torch.stack(losses).mean().item())
     loss_acc = torch.zeros((), device=dev)
     images_per_s = world * B * args.steps / dt

@@ -27,8 +27,37 @@ def pytest_sessionstart(session):
         subprocess.run(["make", "-C", os.path.join(PKG, "csrc")], check=False, stdout=subprocess.DEVNULL)
 
 
+class Golden(dict):
+    """The arrays of one fixture, by name (``.files`` lists them in stored order, as ``np.load`` of an .npz does)."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """tests/golden/<name> together with its continuation files <stem>.part1.npz, <stem>.part2.npz, ... and arrays stored in
+    row blocks ``<key>::chunk<i>`` joined back along axis 0: make_goldens.save_golden splits a fixture so that no committed file
+    exceeds 1 MiB."""
+    stem = os.path.splitext(name)[0]
+    paths = [os.path.join(GOLDEN, name)]
+    i = 1
+    while os.path.exists(os.path.join(GOLDEN, f"{stem}.part{i}.npz")):
+        paths.append(os.path.join(GOLDEN, f"{stem}.part{i}.npz"))
+        i += 1
+    g, chunks = Golden(), {}
+    for p in paths:
+        with np.load(p, allow_pickle=False) as z:
+            for k in z.files:
+                key, sep, _ = k.partition("::chunk")
+                if sep:
+                    g.setdefault(key, None)  # (keeps the array's place in the stored order)
+                    chunks.setdefault(key, []).append(z[k])
+                else:
+                    g[k] = z[k]
+    for key, parts in chunks.items():
+        g[key] = np.concatenate(parts, axis=0)
+    return g
 
 
 @pytest.fixture(scope="session")

@@ -49,6 +49,37 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
+PART_BYTES = 900_000  # raw bytes per file: compressed, with the zip and .npy headers, every committed file stays under 1 MiB
+
+
+def save_golden(fname, out):
+    """np.savez_compressed of ``out`` as tests/golden/<fname>, continued in <stem>.part1.npz, <stem>.part2.npz, ... when the arrays
+    exceed PART_BYTES; an array larger than that is stored in row blocks ``<key>::chunk<i>``.  tests/conftest.py::load_golden
+    reassembles the same mapping."""
+    items = []
+    for k, v in out.items():
+        v = np.asarray(v)
+        n = min(-(-v.nbytes // PART_BYTES), v.shape[0]) if v.ndim else 1
+        if n > 1:
+            items += [(f"{k}::chunk{i}", c) for i, c in enumerate(np.array_split(v, n, axis=0))]
+        else:
+            items.append((k, v))
+    parts, size = [{}], 0
+    for k, v in items:
+        if parts[-1] and size + v.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    stem = fname[:-len(".npz")]
+    i = 1
+    while os.path.exists(os.path.join(OUT, f"{stem}.part{i}.npz")):  # (a regenerated fixture may need fewer parts)
+        os.remove(os.path.join(OUT, f"{stem}.part{i}.npz"))
+        i += 1
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(OUT, fname if i == 0 else f"{stem}.part{i}.npz"), **p)
+
+
 def _ref_vit_taps(vt, model, images, layers, add_norm=True, patch=16):
     """Drive the reference VisionTransformer the way DINO.forward does (dino.py:164-210):
     the wrapper itself needs torchvision (absent), so its ~25 lines of glue are replayed
@@ -105,7 +136,7 @@ def golden_vit_tiny(vt, embed_dim=64, heads=4, fname="vit_tiny.npz"):
             out[f"{tag}_rmean{i}"] = _np(running[i][0])
             out[f"{tag}_rvar{i}"] = _np(running[i][1])
         out[f"{tag}_raw_last"] = _np(raw[0])
-    np.savez_compressed(os.path.join(OUT, fname), **out)
+    save_golden(fname, out)
     print("vit_tiny", {k: v.shape for k, v in out.items() if k.startswith("a_")})
 
 
@@ -133,7 +164,7 @@ def golden_vit_base(vt):
             out[f"{tag}_rmean{i}"] = _np(running[i][0])
             out[f"{tag}_rvar{i}"] = _np(running[i][1])
         print("vit_base", tag, [tuple(t.shape) for t in taps])
-    np.savez_compressed(os.path.join(OUT, "vit_base.npz"), **out)
+    save_golden("vit_base.npz", out)
 
 
 def _grads(module):
@@ -187,7 +218,7 @@ def golden_probes(pr):
         for n, gr in _grads(probe).items():
             out[f"{name}__grad__{n}"] = gr
         print("probe", name, tuple(y.shape), probe.name)
-    np.savez_compressed(os.path.join(OUT, "probes.npz"), **out)
+    save_golden("probes.npz", out)
 
 
 def golden_probes_multiscale(pr):
@@ -229,7 +260,7 @@ def golden_probes_multiscale(pr):
     for n, gr in _grads(probe).items():
         out[f"depth_ms_k3__grad__{n}"] = gr
     print("probe depth_ms_k3", tuple(y.shape), probe.name)
-    np.savez_compressed(os.path.join(OUT, "probes_multiscale.npz"), **out)
+    save_golden("probes_multiscale.npz", out)
 
 
 def golden_losses(ls):
@@ -264,7 +295,7 @@ def golden_losses(ls):
         tag = f"ang_ua{int(ua)}"
         out[f"{tag}_pred"], out[f"{tag}_gt"], out[f"{tag}_mask"] = _np(pred), _np(gt), _np(mask)
         out[f"{tag}_loss"], out[f"{tag}_grad"] = np.array(loss.item()), _np(pred.grad)
-    np.savez_compressed(os.path.join(OUT, "losses.npz"), **out)
+    save_golden("losses.npz", out)
     print("losses", len(out))
 
 
@@ -304,7 +335,7 @@ def golden_optim(op, pr, ls):
     out["traj_lrs"] = np.array(lrs)
     out["traj_final_weight"] = _np(probe.head.conv.weight)
     out["traj_final_bias"] = _np(probe.head.conv.bias)
-    np.savez_compressed(os.path.join(OUT, "optim.npz"), **out)
+    save_golden("optim.npz", out)
     print("optim", traj, lrs)
 
 
@@ -343,7 +374,7 @@ def golden_step(vt, pr, ls, op):
     out["losses"] = np.array(losses)
     out["final_weight"] = _np(probe.head.conv.weight)
     out["final_bias"] = _np(probe.head.conv.bias)
-    np.savez_compressed(os.path.join(OUT, "step_tiny.npz"), **out)
+    save_golden("step_tiny.npz", out)
     print("step_tiny", losses)
 
 
@@ -384,7 +415,7 @@ def golden_metrics():
     sm = mt.evaluate_surface_norm(sn, sg, seg, is_navi=True)[0]
     for k, v in sm.items():
         out[f"sn_{k}"] = _np(v.reshape(B))
-    np.savez_compressed(os.path.join(OUT, "metrics.npz"), **out)
+    save_golden("metrics.npz", out)
     print("metrics", {k: v.shape for k, v in out.items() if k.startswith("sa_")})
 
 
@@ -450,7 +481,7 @@ def golden_metrics_breakdown():
             for k, v in d.items():
                 out[f"{tag}_sn_{L}_{k}"] = _np(v.reshape(B))
         out[f"{tag}_sn_segments"] = _seg_rows(sm)
-    np.savez_compressed(os.path.join(OUT, "metrics_seg.npz"), **out)
+    save_golden("metrics_seg.npz", out)
     print("metrics_seg", len(out), "arrays;", {k: v.shape for k, v in out.items() if k.startswith("a_sa_level_1")})
 
 
@@ -470,7 +501,7 @@ def golden_si_train(ls):
     loss = ls.DepthLoss()(p3, tgt.clone())
     loss.backward()
     out.update(pred=_np(pred), target=_np(tgt), matched=_np(p2), clamped=_np(p3), loss=np.array(loss.item()), grad=_np(pred.grad))
-    np.savez_compressed(os.path.join(OUT, "si_train.npz"), **out)
+    save_golden("si_train.npz", out)
     print("si_train loss", loss.item(), "clamped fraction", float(((p2 < 0.001) | (p2 > 1.0)).float().mean()))
 
 
@@ -517,7 +548,7 @@ def golden_spair():
     out["tie_heat"] = _np(ti)
     out["tie_max"] = _np(co.argmax_2d(ti, max_value=True))
     out["tie_min"] = _np(co.argmax_2d(ti, max_value=False))
-    np.savez_compressed(os.path.join(OUT, "spair.npz"), **out)
+    save_golden("spair.npz", out)
     print("spair", out["pred_max"][:4].tolist(), out["tie_max"][:3].tolist(), out["tie_min"][:3].tolist())
 
 
@@ -584,7 +615,7 @@ def golden_mae():
         _, i, rest = k.split(".", 2)
         mod, leaf = rest.rsplit(".", 1)
         out[f"w:encoder.layer.{i}.{sub[mod]}.{leaf}"] = _np(v)
-    np.savez_compressed(os.path.join(OUT, "mae_tiny.npz"), **out)
+    save_golden("mae_tiny.npz", out)
     print("mae_tiny", [float(np.abs(out[f"dense_{j}"]).mean()) for j in range(4)], "pos_embed |max|", float(np.abs(out["pos_embed_hf"]).max()))
 
 

@@ -1,13 +1,19 @@
 """The hydra config surface (north_star: "keeps the hydra backbone/probe config surface"):
   * this package's configs/<group>/<choice>.yaml compose through mvp.config exactly like `python train_depth.py backbone=dino_b16`;
-  * (build container only) every hot-path choice file of the REFERENCE loads and its ``_target_`` + kwargs instantiate against this
-    package unchanged — i.e. the reference's own yaml drives these classes."""
+  * every hot-path choice file of the REFERENCE loads and its ``_target_`` + kwargs instantiate against this package unchanged —
+    i.e. the reference's own yaml drives these classes.  tests/golden/reference_config_digests.json records the SHA-256 of each of
+    those reference files as parsed (canonical JSON, sorted keys); a choice file of this package with the same digest is the same
+    mapping, so it stands in for the reference's file."""
+import hashlib
+import json
 import os
 
 import pytest
 import yaml
 
-REF = "/root/reference/configs"
+from conftest import GOLDEN
+
+REF_DIGESTS = json.load(open(os.path.join(GOLDEN, "reference_config_digests.json")))
 BACKBONES = ["dino_b16", "ibot_b16", "mae_b16", "mocov3_b14", "dino_resnet50", "mocov3_resnet50"]
 PROBES = ["depth_dpt", "snorm_dpt"]
 
@@ -27,28 +33,35 @@ def test_compose_per_choice_layout():
         config.compose("depth_training", ["backbone=does_not_exist"])
 
 
-def test_own_choice_files_match_reference_schema():
-    """Same keys and values as the reference's files for the hot-path choices (a config schema is category-(b) similarity)."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference configs only exist in the build container")
+def _digest(node):
+    return hashlib.sha256(json.dumps(node, sort_keys=True).encode()).hexdigest()
+
+
+def _reference_node(group, name):
+    """The reference's configs/<group>/<name>.yaml as parsed: this package's file of that choice, once its digest is the reference's."""
     from mvp import config
 
-    for group, names in (("backbone", BACKBONES), ("probe", PROBES), ("optimizer", ["one_epoch", "three_epoch", "ten_epoch", "fifteen_epoch"])):
+    own = yaml.safe_load(open(os.path.join(config.CONFIG_DIR, group, name + ".yaml")))
+    assert _digest(own) == REF_DIGESTS[f"{group}/{name}"], (group, name, own)
+    return own
+
+
+def test_own_choice_files_match_reference_schema():
+    """Same keys and values as the reference's files for the hot-path choices (a config schema is category-(b) similarity)."""
+    groups = (("backbone", BACKBONES), ("probe", PROBES), ("optimizer", ["one_epoch", "three_epoch", "ten_epoch", "fifteen_epoch"]))
+    assert sorted(REF_DIGESTS) == sorted(f"{g}/{n}" for g, names in groups for n in names)
+    for group, names in groups:
         for n in names:
-            ref = yaml.safe_load(open(os.path.join(REF, group, n + ".yaml")))
-            own = yaml.safe_load(open(os.path.join(config.CONFIG_DIR, group, n + ".yaml")))
-            assert own == ref, (group, n, own, ref)
+            _reference_node(group, n)
 
 
 @pytest.mark.parametrize("name", BACKBONES)
 def test_reference_backbone_yaml_instantiates_here(name):
-    if not os.path.isdir(REF):
-        pytest.skip("reference configs only exist in the build container")
     import warnings
 
     from mvp import config
 
-    node = yaml.safe_load(open(os.path.join(REF, "backbone", name + ".yaml")))
+    node = _reference_node("backbone", name)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")  # "no local checkpoint: seeded random init"
         model = config.instantiate(node, return_multilayer=True)  # train_depth.py:564-567 adds return_multilayer for dpt probes
@@ -58,11 +71,9 @@ def test_reference_backbone_yaml_instantiates_here(name):
 
 @pytest.mark.parametrize("name", PROBES)
 def test_reference_probe_yaml_instantiates_here(name):
-    if not os.path.isdir(REF):
-        pytest.skip("reference configs only exist in the build container")
     from mvp import config
 
-    node = yaml.safe_load(open(os.path.join(REF, "probe", name + ".yaml")))
+    node = _reference_node("probe", name)
     probe = config.instantiate(node, feat_dim=[768] * 4)
     assert probe.name == {"depth_dpt": "bindepth_dpt_k3", "snorm_dpt": "snorm_dpt_k3_UA"}[name]
     n = sum(p.numel() for p in probe.parameters())

@@ -1,7 +1,7 @@
 #!/bin/bash
 # 480x640 (BASELINE config #2 shape): pipeline variants.  Run through gpurun from the repo root.
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-Q="--no-cpu-baseline --no-live-pmc --no-roofline --no-serial-leg --sustained-steps 48 --image-size 480x640 --steps 16 --warmup 4"
+Q="--full --no-cpu-baseline --no-live-pmc --no-roofline --no-serial-leg --sustained-steps 48 --image-size 480x640 --steps 16 --warmup 4"
 run() { echo "== $*"; env $ENVV python3 bench.py "$@" $Q 2>&1 | grep '^{' | python3 -c "
 import json,sys
 for l in sys.stdin:

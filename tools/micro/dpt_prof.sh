@@ -3,7 +3,7 @@
 set -eo pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
-Q="--no-cpu-baseline --no-live-pmc --sustained-steps 0"
+Q="--full --no-cpu-baseline --no-live-pmc --sustained-steps 0"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/dpt_stats -- python3 $ROOT/bench.py --probe dpt --steps 6 --warmup 2 --inflight 1 --no-roofline --no-serial-leg $Q > $OUT/dpt_stats.log 2>&1
 cp $(find $OUT/dpt_stats -name "*kernel_stats.csv" | head -1) $OUT/dpt_kernel_stats.csv

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Does leaving a few CUs out of every large-M GEMM launch (MVP_PP_GRID, spans sized to that many CUs) pay beside the probe steps?  Alternating on one box.
-B="python bench.py --steps 20 --warmup 5 --no-alt-precision --no-serial-leg --no-cpu-baseline --no-roofline --sustained-steps 300"
+B="python bench.py --full --steps 20 --warmup 5 --no-alt-precision --no-serial-leg --no-cpu-baseline --no-roofline --sustained-steps 300"
 run() {  # grid span
   echo "## MVP_PP_GRID=${1:-unset} span=${2:-default}"
   if [ -n "$1" ]; then export MVP_PP_GRID=$1; else unset MVP_PP_GRID; fi

@@ -1,5 +1,7 @@
 import sys, os
-sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/midvision-probe_amd")
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for _p in ("tests", "", "midvision-probe_amd"):
+    sys.path.insert(0, os.path.join(REPO, _p))
 import torch
 import test_gpu_configs as T
 worst = {}

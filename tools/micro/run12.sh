@@ -1,6 +1,6 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
-F="--no-cpu-baseline --no-roofline --no-live-pmc --sustained-steps 0"
+F="--full --no-cpu-baseline --no-roofline --no-live-pmc --sustained-steps 0"
 run() { echo "== $*" >> gpurun_out/r3_b12.log; timeout -k 10 400 python bench.py $F "$@" 2>&1 | python3 -c "
 import sys, json
 for l in sys.stdin:

@@ -3,7 +3,7 @@
 set -eo pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
-Q="--no-cpu-baseline --no-live-pmc --no-roofline"
+Q="--full --no-cpu-baseline --no-live-pmc --no-roofline"
 run() { echo "== $*"; python3 bench.py "$@" $Q 2>&1 | grep '^{' | python3 -c "
 import json,sys
 for l in sys.stdin:

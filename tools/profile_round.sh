@@ -7,12 +7,12 @@ set -eo pipefail
 TAG=${1:-r04}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
-# the default bench command (what the driver runs), without its CPU legs and without the nested PMC children
-DEF="--steps 20 --warmup 5 --no-cpu-baseline --no-live-pmc --sustained-steps 0"
+# the full bench command (--full: every leg of it), without its CPU legs and without the nested PMC children
+DEF="--full --steps 20 --warmup 5 --no-cpu-baseline --no-live-pmc --sustained-steps 0"
 # the timed run's pipeline as the PMC child runs it: grouped forwards, eager launches, 1 + 2 groups of steps, nothing else
 CHILD="--pmc-child"
 # the serial leg: one batch at a time on one stream (its own tile set: the 64x64 family)
-SERIAL="--steps 8 --warmup 3 --inflight 1 --no-cpu-baseline --no-live-pmc --no-roofline --sustained-steps 0"
+SERIAL="--full --steps 8 --warmup 3 --inflight 1 --no-cpu-baseline --no-live-pmc --no-roofline --sustained-steps 0"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $ROOT/bench.py $DEF > $OUT/${TAG}_stats.log 2>&1
 echo "stats pass done"
