@@ -63,7 +63,10 @@ typedef struct {
   int cu_count;         /* multiProcessorCount of device 0                   */
   char arch[64];        /* gcnArchName of device 0                           */
 } mvp_info_t;
-#define MVP_ABI_VERSION 7 /* 7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6
+#define MVP_ABI_VERSION 7 /* 7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
+                                Later additions within 7 (new exports with their own argument structs; no existing struct changed):
+                                mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
+                                their argument structs are tagged structs (struct X {...}; typedef'd ahead), the ABI 7 set of `} mvp_*;` structs is unchanged
                              6: mvp_gemm_args.out_f16_col0, mvp_attention_args.v_format (both structs grew by one int at the end; zero = the ABI 5 behaviour)
                              5: mvp_upconv3_fwd_gather, mvp_upconv3_grad_boxsum; mvp_gemm_pp accepts conv; depth-loss workspace grew (query mvp_depth_loss_workspace_bytes) */
 int mvp_get_info(mvp_info_t* out);
@@ -98,6 +101,14 @@ typedef struct {
   int pad_top, pad_left;
 } mvp_patch_gather_args;
 int mvp_patch_gather(const mvp_patch_gather_args*, void* stream);
+/* The same gather into rows of ldk >= C*P*P elements, columns [C*P*P, ldk) written as zeros, and any P >= 1 (DINOv2: P = 14,
+ * C*P*P = 588 padded to ldk = 608 so that the patch-embed GEMM gets K % 32 == 0; its weights are padded with zero columns once). */
+typedef struct mvp_patch_gather_ld_args mvp_patch_gather_ld_args;
+struct mvp_patch_gather_ld_args {
+  mvp_patch_gather_args g;
+  int ldk;             /* row stride of out_hi / out_lo, elements; % 4 == 0     */
+};
+int mvp_patch_gather_ld(const mvp_patch_gather_ld_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * GEMM with fused epilogue:   Y = act(A · Wᵀ + bias) + residual
@@ -199,6 +210,18 @@ int mvp_gemm_pp(const mvp_gemm_args*, void* stream);
 int64_t mvp_gemm_splitk_workspace_bytes(int M, int N, int splits);
 int64_t mvp_gemm_streamk_workspace_bytes(void);
 int mvp_gemm_streamk(const mvp_gemm_args*, void* stream);  /* what mvp_gemm_bias_act_res dispatches to for splitk == MVP_GEMM_STREAMK */
+/* LayerScale fused into the epilogue (DINOv2 blocks: x + ls1.gamma * proj(.), x + ls2.gamma * fc2(.)):
+ *   Y[m, n] = col_scale[n] * act(A · Wᵀ + bias)[m, n] + residual
+ * i.e. the scale is applied after bias and activation, before the residual add.  `gemm` keeps mvp_gemm_bias_act_res's contract and
+ * tile / large-M dispatch (both pair layouts, every precision); not supported (MVP_EINVAL): convolutions, split-K, stream-K, masks,
+ * pair residuals, residual2, act_after_res.  The scale is NOT folded into the weights: a tiny gamma (1e-5) would push the fp16 halves
+ * of the MVP_PREC_F16X2 weight pairs into subnormals.  col_scale: [N] fp32, 16-byte aligned.                                       */
+typedef struct mvp_gemm_scaled_args mvp_gemm_scaled_args;
+struct mvp_gemm_scaled_args {
+  mvp_gemm_args gemm;
+  const float* col_scale;
+};
+int mvp_gemm_scaled(const mvp_gemm_scaled_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * LayerNorm forward: fp32 rows [M, C] -> bf16 pair [M, C] (the next GEMM's A operand).
@@ -256,6 +279,13 @@ typedef struct {
   const float* cls; const float* pos0; float* x; int B, N, C;
 } mvp_cls_rows_args;
 int mvp_cls_rows(const mvp_cls_rows_args*, void* stream);
+/* Prefix rows of every image in one launch: x[b, 0, :] = cls + pos0, x[b, 1 + r, :] = reg[r, :] for r < R (DINOv2 register tokens:
+ * no position embedding).  R = 0 is mvp_cls_rows.  The patch rows follow at 1 + R (patch-embed GEMM: row_group_off = 1 + R). */
+typedef struct mvp_prefix_rows_args mvp_prefix_rows_args;
+struct mvp_prefix_rows_args {
+  const float* cls; const float* pos0; const float* reg; float* x; int B, N, C, R;
+};
+int mvp_prefix_rows(const mvp_prefix_rows_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Tap BatchNorm over tokens (train-mode batch statistics, CLS included) fused with the

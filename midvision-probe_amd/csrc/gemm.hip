@@ -56,8 +56,9 @@ constexpr int SPLITK_CTR_BYTES = 65536;
 // runs the normal fused epilogue.  The counter resets itself for the next launch.
 // NW = waves per workgroup (4: 2x2 wave grid; 8: 4x2, i.e. the same tile cut into more, smaller wave tiles).
 // WNW = waves along N (the wave grid is (NW / WNW) x WNW).
-template <int BM, int BN, int BK, int SPLIT, int NSTAGE, bool CONV, bool EXT, bool KSPLIT = false, int NW = 4, int WNW = 2>
-__global__ __launch_bounds__(NW * 64) void gemm_kernel(const mvp_gemm_args p) {
+// KA: mvp_gemm_args, or mvp_gemm_kscaled (LayerScale applied by the epilogue: mvp_gemm_scaled).
+template <int BM, int BN, int BK, int SPLIT, int NSTAGE, bool CONV, bool EXT, bool KSPLIT = false, int NW = 4, int WNW = 2, class KA = mvp_gemm_args>
+__global__ __launch_bounds__(NW * 64) void gemm_kernel(const KA p) {
   static_assert(!(KSPLIT && (CONV || EXT)), "split-K is compiled for the plain linear GEMMs only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NARR = (SPLIT >= 2) ? 2 : 1;  // SPLIT 3: bf16 pairs, three products; 2 (MVP_PREC_F16X2): fp16 hi + bf16 lo activations, two products
@@ -381,10 +382,20 @@ constexpr int gemm_smem() {
   return stages > epi ? stages : epi;
 }
 
-template <int BM, int BN, int BK, int SPLIT, int NSTAGE, bool CONV = false, int NW = 4, int WNW = 2>
-int launch_gemm(const mvp_gemm_args* a, hipStream_t s) {
+template <int BM, int BN, int BK, int SPLIT, int NSTAGE, bool CONV = false, int NW = 4, int WNW = 2, class KA = mvp_gemm_args>
+int launch_gemm(const KA* a, hipStream_t s) {
   constexpr int SMEM = gemm_smem<BM, BN, BK, SPLIT, NSTAGE, NW, WNW>();
   static_assert(SMEM <= 160 * 1024, "LDS budget");
+  if constexpr (has_col_scale<KA>::value) {  // LayerScale: the plain (non-EXT) instantiation only (mvp_gemm_scaled refused the rest)
+    static_assert(!CONV, "LayerScale GEMMs are plain linear GEMMs");
+    static int configured_s = (int)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, BK, SPLIT, NSTAGE, false, false, false, NW, WNW, KA>,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+    if (configured_s != 0) return MVP_ELAUNCH;
+    const int tiles_s = ((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN);
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, SPLIT, NSTAGE, false, false, false, NW, WNW, KA>), dim3(tiles_s), dim3(NW * 64), SMEM, s, *a);
+    MVP_LAUNCH_CHECK();
+    return MVP_OK;
+  }
   static int configured = [] {
     int e = (int)hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, BK, SPLIT, NSTAGE, CONV, false, false, NW, WNW>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
@@ -474,16 +485,27 @@ static bool pp_takes(const mvp_gemm_args* a) {
   return t >= 200 && (t * 5 >= rounds * 256 * 4 || t >= 1024);
 }
 
-extern "C" int mvp_gemm_bias_act_res(const mvp_gemm_args* a, void* stream) {
+// mvp_gemm_bias_act_res (KA = mvp_gemm_args) and mvp_gemm_scaled (KA = mvp_gemm_kscaled, which the caller restricted to plain linear
+// GEMMs without split-K / stream-K): one validation and one tile rule for both.
+template <class KA>
+static int gemm_dispatch(const KA* a, void* stream) {
+  constexpr bool SC = has_col_scale<KA>::value;
   if (!a || !a->a_hi || !a->w_hi) return MVP_EINVAL;
-  if (a->splitk == MVP_GEMM_STREAMK) return a->out_f16_col0 ? MVP_EINVAL : mvp_gemm_streamk(a, stream);
+  if constexpr (!SC) {
+    if (a->splitk == MVP_GEMM_STREAMK) return a->out_f16_col0 ? MVP_EINVAL : mvp_gemm_streamk(a, stream);
+  }
   if (a->pair_layout < 0 || a->pair_layout > MVP_PAIR_ILV32) return MVP_EINVAL;
   if (a->out_pair_layout != MVP_PAIR_SEPARATE &&
       (a->out_pair_layout != MVP_PAIR_A_ILV32 || !a->out_hi || (a->N & 31) || (a->precision != MVP_PREC_BF16X3 && a->precision != MVP_PREC_F16X2))) return MVP_EINVAL;
   if (a->out_f16_col0 != 0 && ((a->out_f16_col0 != -1 && ((a->out_f16_col0 < 0 ? -a->out_f16_col0 : a->out_f16_col0) & (a->out_f16_col0 < 0 ? 127 : 63))) || (a->precision != MVP_PREC_BF16X3 && a->precision != MVP_PREC_F16X2) || !a->out_hi ||
                                (!a->out_lo && a->out_pair_layout == MVP_PAIR_SEPARATE) || a->splitk > 1))
     return MVP_EINVAL;
-  if (a->M > 0 && a->N > 0 && (a->out_f32 || a->out_hi) && pp_takes(a)) return mvp_gemm_pp(a, stream);
+  if (a->M > 0 && a->N > 0 && (a->out_f32 || a->out_hi) && pp_takes(a)) {
+    if constexpr (SC)
+      return mvp_gemm_pp_scaled(a, stream);
+    else
+      return mvp_gemm_pp(a, stream);
+  }
   if (a->pair_layout != MVP_PAIR_SEPARATE) return MVP_EINVAL;  // the tile kernels read separate hi / lo arrays
   if (a->M <= 0 || a->N <= 0 || a->K <= 0 || (a->K & (a->conv ? 31 : 63))) {
     // the one non-conv exception: K % 32 == 0 through the BK = 32 two-stage tile (ResNet stem: K = 147 padded to 160)
@@ -504,6 +526,7 @@ extern "C" int mvp_gemm_bias_act_res(const mvp_gemm_args* a, void* stream) {
   if (!a->out_f32 && !a->out_hi) return MVP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const bool x3 = a->precision == MVP_PREC_BF16X3;
+  if constexpr (!SC) {
   if (a->conv) {
     if (!a->zero_page || a->cC <= 0 || (a->cC & 31) || a->ckh <= 0 || a->ckw <= 0 || a->cstride <= 0) return MVP_EINVAL;
     if (a->K != a->ckh * a->ckw * a->cC || a->cHo <= 0 || a->cWo <= 0 || (a->M % (a->cHo * a->cWo))) return MVP_EINVAL;
@@ -526,12 +549,15 @@ extern "C" int mvp_gemm_bias_act_res(const mvp_gemm_args* a, void* stream) {
     if (a->N > 64) return x3 ? launch_gemm<128, 128, 32, 3, 2, true>(a, s) : launch_gemm<128, 128, 32, 1, 2, true>(a, s);
     return x3 ? launch_gemm<128, 64, 32, 3, 2, true>(a, s) : launch_gemm<128, 64, 32, 1, 2, true>(a, s);
   }
+  }
   if (a->K & 63) return launch_gemm<128, 64, 32, 3, 2>(a, s);
+  if constexpr (!SC) {
   const bool ext = a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi;
   if (a->splitk > 1 && !ext) {  // (with the ReLU-gate / second-residual epilogues the request is ignored)
     if (a->splitk > 64 || a->K / 64 < a->splitk) return MVP_EINVAL;
     if (splitk_wide(a->N)) return x3 ? launch_gemm_splitk<128, 128, 64, 3, 1>(a, s) : launch_gemm_splitk<128, 128, 64, 1, 2>(a, s);
     return x3 ? launch_gemm_splitk<128, 64, 64, 3, 1>(a, s) : launch_gemm_splitk<128, 64, 64, 1, 2>(a, s);
+  }
   }
 #ifdef MVP_F_BM
 #ifndef MVP_F_NW
@@ -586,4 +612,17 @@ extern "C" int mvp_gemm_bias_act_res(const mvp_gemm_args* a, void* stream) {
   if (t128 >= 400) return launch_gemm<128, 128, 64, 1, 2>(a, s);
   return launch_gemm<64, 64, 64, 1, 2>(a, s);
 #endif
+}
+
+extern "C" int mvp_gemm_bias_act_res(const mvp_gemm_args* a, void* stream) { return gemm_dispatch(a, stream); }
+
+extern "C" int mvp_gemm_scaled(const mvp_gemm_scaled_args* a, void* stream) {
+  if (!a || !a->col_scale || ((size_t)a->col_scale & 15)) return MVP_EINVAL;
+  const mvp_gemm_args& g = a->gemm;
+  // plain linear GEMMs: no convolution, split-K / stream-K or EXT epilogue features (masks, pair residuals, residual2, act_after_res)
+  if (g.conv || (g.splitk != 0 && g.splitk != 1) || g.relu_mask || g.out_mask || g.residual2 || g.act_after_res || g.residual_hi) return MVP_EINVAL;
+  mvp_gemm_kscaled k;
+  static_cast<mvp_gemm_args&>(k) = g;
+  k.col_scale = a->col_scale;
+  return gemm_dispatch(&k, stream);
 }

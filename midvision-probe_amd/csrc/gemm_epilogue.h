@@ -2,6 +2,9 @@
 // LDS-staged epilogue.  Header-only, force-inlined: each kernel keeps its own main loop and calls gemm_epilogue() once its
 // accumulators are final and every wave is done with the staging buffers (the caller's barrier).
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "mvp_common.h"
 
 // Cache policy of the wide epilogue's output stores (gfx940+ aux bits: 1 = sc0, 2 = nt, 16 = sc1; profiles/r04_store_policy.txt).
@@ -28,7 +31,27 @@
 #define MVP_EPI_UNI_NT 0
 #endif
 
+// Kernel arguments of the LayerScale GEMMs (mvp_gemm_scaled): the plain arguments plus the per-column scale, one struct so that every
+// field keeps its name (the epilogues read p.M, p.bias ... either way).  The epilogues apply the scale when their ARGS type has it — a
+// compile-time property: the instantiations of mvp_gemm_bias_act_res are the ones they were.
+struct mvp_gemm_kscaled : mvp_gemm_args {
+  const float* col_scale;
+};
+// gemm_pp.hip's entry for these arguments (mvp_gemm_scaled in gemm.hip dispatches to it by the same rule as mvp_gemm_bias_act_res)
+__attribute__((visibility("hidden"))) int mvp_gemm_pp_scaled(const mvp_gemm_kscaled* a, void* stream);
+
 namespace {
+template <class T, class = void>
+struct has_col_scale : std::false_type {};
+template <class T>
+struct has_col_scale<T, std::void_t<decltype(std::declval<T&>().col_scale)>> : std::true_type {};
+
+// The LayerScale product, never contracted with the residual add that follows it: the epilogues differ in what the compiler could fuse
+// it with, and a batch must get the same bits whichever GEMM kernel its forward uses (see gelu_erf below).
+__device__ __forceinline__ float layer_scale(float v, float s) {
+#pragma clang fp contract(off)
+  return v * s;
+}
 
 // Branch-free erf GELU: Abramowitz-Stegun 7.1.26 for 1 - erf (|erf error| <= 1.5e-7), one v_exp + one v_rcp.  (ocml erff measured
 // ~17 us of VALU on the fc1 epilogue.)  Round 4 (the fc1 epilogue is bound by its vector instructions — 26 per value with the operand
@@ -106,6 +129,7 @@ __device__ __forceinline__ void gemm_epilogue(const ARGS& p, f32x4_t (&acc)[NT][
   // retired every read of the staging buffers, so they can be reused.
   constexpr int EPW = WN + 4;                 // padded row, floats (conflict-free b128 write/read)
   constexpr int EP_BYTES = 32 * EPW * 4;      // per wave
+  constexpr bool SC = has_col_scale<ARGS>::value;
   constexpr int LPR = WN / 4;                 // lanes per output row (16 or 8)
   constexpr int RPI = 64 / LPR;               // rows per wave-instruction (4 or 8)
   float* ep = (float*)(smem + wave * EP_BYTES);
@@ -117,6 +141,14 @@ __device__ __forceinline__ void gemm_epilogue(const ARGS& p, f32x4_t (&acc)[NT][
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (ncol + e < p.N) bias4[e] = p.bias[ncol + e];
+  }
+  float scale4[4] = {1.f, 1.f, 1.f, 1.f};
+  if constexpr (SC) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (ncol + e < p.N) scale4[e] = p.col_scale[ncol + e];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) asm volatile("" : "+v"(scale4[e]));
   }
   // An unconditional use right here: the compiler waits for the bias loads ONCE, before any store is issued.  Their only other
   // uses sit inside the row loop's `m < M` regions, and its wait-count pass must assume that a skipped row leaves them pending —
@@ -152,6 +184,10 @@ __device__ __forceinline__ void gemm_epilogue(const ARGS& p, f32x4_t (&acc)[NT][
       } else if (p.act == MVP_ACT_RELU && !x_act_after) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      }
+      if constexpr (SC) {  // LayerScale: after bias and activation, before the residual
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = layer_scale(v[e], scale4[e]);
       }
       auto write_mask = [&]() {  // forward: remember which outputs the ReLU kept (its backward gate)
         uint8_t* mo = x_out_mask + (size_t)orow * p.ldm + ncol;
@@ -324,6 +360,15 @@ __device__ __forceinline__ void gemm_epilogue_wide(const ARGS& p, f32x4_t (&acc)
   const int lo_soff = oilv ? 64 : 0;
   const int ob = col_ok ? ncol * 4 : SENT;
   const u32x4_t bias_a = __builtin_amdgcn_raw_buffer_load_b128(r_bias, ob, 0, 0), bias_b = __builtin_amdgcn_raw_buffer_load_b128(r_bias, ob, 16, 0);
+  // LayerScale (ARGS = mvp_gemm_kscaled): two more loads beside the bias — issued before the caller's hook like the bias, so the caller's
+  // count of the operations issued AFTER the hook (gemm_epilogue_wide_ops::after_hook) is unchanged
+  constexpr bool SC = has_col_scale<ARGS>::value;
+  u32x4_t scale_a = u32x4_t{0u, 0u, 0u, 0u}, scale_b = u32x4_t{0u, 0u, 0u, 0u};
+  if constexpr (SC) {
+    const __amdgpu_buffer_rsrc_t r_scale = rsrc(p.col_scale);
+    scale_a = __builtin_amdgcn_raw_buffer_load_b128(r_scale, ob, 0, 0);
+    scale_b = __builtin_amdgcn_raw_buffer_load_b128(r_scale, ob, 16, 0);
+  }
   // row m of the tile -> byte offsets into the output / residual / gate arrays (the sentinel for rows past M and columns past N)
   const int pcol = PAIR ? (oilv ? ilv32_col(ncol) : ncol) : 0;
   struct row_off { int out, res, gate; };
@@ -364,9 +409,13 @@ __device__ __forceinline__ void gemm_epilogue_wide(const ARGS& p, f32x4_t (&acc)
   };
   load_res(0);
   after_first_loads();
-  float bias8[8];
+  float bias8[8], scale8[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) { bias8[e] = u2f(bias_a[e]); bias8[4 + e] = u2f(bias_b[e]); }
+  if constexpr (SC) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { scale8[e] = u2f(scale_a[e]); scale8[4 + e] = u2f(scale_b[e]); }
+  }
 #pragma unroll
   for (int u = 0; u < MT; ++u) {
     // (straight-line code: without the fence the scheduler pulls the LDS round trips and residual loads of later units forward until
@@ -386,6 +435,10 @@ __device__ __forceinline__ void gemm_epilogue_wide(const ARGS& p, f32x4_t (&acc)
       if (ACT == MVP_ACT_GELU) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[it][e] = gelu_erf(v[it][e]);
+      }
+      if constexpr (SC) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = layer_scale(v[it][e], scale8[e]);
       }
       if (GATE) {
 #pragma unroll
@@ -490,6 +543,13 @@ __device__ __forceinline__ void gemm_epilogue_uni(const ARGS& p, f32x4_t (&acc)[
   const int pform = has_pair ? out_pair_form(p.out_f16_col0, n0 + wn0) : 0;  // (wave-uniform: every boundary is a multiple of 64)
   const int ob = col_ok ? ncol * 4 : SENT;
   const u32x4_t bias_a = __builtin_amdgcn_raw_buffer_load_b128(r_bias, ob, 0, 0), bias_b = __builtin_amdgcn_raw_buffer_load_b128(r_bias, ob, 16, 0);
+  constexpr bool SC = has_col_scale<ARGS>::value;  // LayerScale (mvp_gemm_kscaled): loaded beside the bias, applied before the residuals
+  u32x4_t scale_a = u32x4_t{0u, 0u, 0u, 0u}, scale_b = u32x4_t{0u, 0u, 0u, 0u};
+  if constexpr (SC) {
+    const __amdgpu_buffer_rsrc_t r_scale = rsrc(p.col_scale);
+    scale_a = __builtin_amdgcn_raw_buffer_load_b128(r_scale, ob, 0, 0);
+    scale_b = __builtin_amdgcn_raw_buffer_load_b128(r_scale, ob, 16, 0);
+  }
   const int pcol = oilv ? ilv32_col(ncol) : ncol;
   struct row_off { int o32, opair, res, rpair, mask; };
   auto offsets = [&](int m) {
@@ -526,9 +586,13 @@ __device__ __forceinline__ void gemm_epilogue_uni(const ARGS& p, f32x4_t (&acc)[
   };
   load_next(0);
   after_first_loads();
-  float bias8[8];
+  float bias8[8], scale8[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) { bias8[e] = u2f(bias_a[e]); bias8[4 + e] = u2f(bias_b[e]); }
+  if constexpr (SC) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { scale8[e] = u2f(scale_a[e]); scale8[4 + e] = u2f(scale_b[e]); }
+  }
 #pragma unroll
   for (int u = 0; u < MT; ++u) {
     __builtin_amdgcn_sched_barrier(0);  // (straight-line code: keep the scheduler from pulling later units forward until the registers run out)
@@ -549,6 +613,10 @@ __device__ __forceinline__ void gemm_epilogue_uni(const ARGS& p, f32x4_t (&acc)[
       } else if (p.act == MVP_ACT_RELU && !act_after) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[it][e] = fmaxf(v[it][e], 0.f);
+      }
+      if constexpr (SC) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = layer_scale(v[it][e], scale8[e]);
       }
       mbits[it][0] = mbits[it][1] = 0u;
       if (EXT && x_omask && !act_after) {

@@ -100,8 +100,9 @@ constexpr int PP_SMEM = 2 * PP_BUF_B;    // two k-step buffers = 128 KiB
 // acc += a_lo . w_lo, then acc += a_hi . w_hi, both f16 MFMAs.  Same arrays, layouts, staging and fragment reads (the halves are
 // 16-bit either way); per 32-deep k-step lo product first, then hi, k ascending — the order the tile kernels use, so the two families
 // stay bit-identical in this mode too.
-template <bool ILVA, bool ILVW, bool EXT, bool CONV = false, bool F16X2 = false>
-__global__ __launch_bounds__(512) void gemm_pp_kernel(const mvp_gemm_args p) {
+// KA: mvp_gemm_args, or mvp_gemm_kscaled (LayerScale in the epilogue: mvp_gemm_scaled).
+template <bool ILVA, bool ILVW, bool EXT, bool CONV = false, bool F16X2 = false, class KA = mvp_gemm_args>
+__global__ __launch_bounds__(512) void gemm_pp_kernel(const KA p) {
   static_assert(!(CONV && ILVA), "the convolution reads separate hi / lo activation arrays");
   static_assert(!(F16X2 && (CONV || EXT)), "the two-product mode serves the plain linear GEMMs of the ViT blocks");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const mvp_gemm_args p) {
   int a_voff[4], w_voff[4];  // per-lane byte offsets of this wave's pieces: [HA0 e0, HA0 e1, HA1 e0, HA1 e1], [HB 0..3]
   int cv_img[4], cv_yx[4];   // (conv) per piece row: byte offset of its image, top-left input coordinates (y << 16 | x, biased by 0x4000)
   int ct_ky[2], ct_kx[2], ct_c0[2];  // (conv) tap and channel of the NEXT k-step each half stages (k ascending per half)
-  typedef const __attribute__((address_space(4))) mvp_gemm_args kargs_t;  // the arguments, read in place from the kernel-argument segment
+  typedef const __attribute__((address_space(4))) KA kargs_t;  // the arguments, read in place from the kernel-argument segment
   auto setup_tile = [&](int bid) {
     lane_s = lane;
     asm volatile("" : "+v"(lane_s));
@@ -450,7 +451,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const mvp_gemm_args p) {
     // (and the kernel arguments read afresh from the kernel-argument segment through an opaque pointer, for the same reason: hoisted
     // out of the tile loop the epilogue's ~60 scalars do not fit beside the main loop's and get spilled to VGPR lanes)
 #if MVP_PP_NOLOOP
-    const mvp_gemm_args& pe = p;
+    const KA& pe = p;
 #else
     kargs_t* kp = (kargs_t*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(kp));
@@ -546,11 +547,11 @@ inline int pp_grid(const mvp_gemm_args* a) {
   return (persist && cus >= 8 && tiles > cus) ? cus : tiles;
 }
 
-template <bool ILVA, bool ILVW>
-int launch_pp_f16x2(const mvp_gemm_args* a, hipStream_t s) {  // MVP_PREC_F16X2: plain epilogues only (the caller checked)
-  static int configured = (int)hipFuncSetAttribute((const void*)gemm_pp_kernel<ILVA, ILVW, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_SMEM);
+template <bool ILVA, bool ILVW, class KA>
+int launch_pp_f16x2(const KA* a, hipStream_t s) {  // MVP_PREC_F16X2: plain epilogues only (the caller checked)
+  static int configured = (int)hipFuncSetAttribute((const void*)gemm_pp_kernel<ILVA, ILVW, false, false, true, KA>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_SMEM);
   if (configured != 0) return MVP_ELAUNCH;
-  hipLaunchKernelGGL((gemm_pp_kernel<ILVA, ILVW, false, false, true>), dim3(pp_grid(a)), dim3(512), PP_SMEM, s, *a);
+  hipLaunchKernelGGL((gemm_pp_kernel<ILVA, ILVW, false, false, true, KA>), dim3(pp_grid(a)), dim3(512), PP_SMEM, s, *a);
   MVP_LAUNCH_CHECK();
   return MVP_OK;
 }
@@ -575,9 +576,20 @@ int launch_pp(const mvp_gemm_args* a, hipStream_t s) {
   return MVP_OK;
 }
 
-}  // namespace
+// LayerScale GEMMs: the plain (non-EXT) instantiation only — the wide epilogues where they serve, the generic one otherwise (the caller
+// refused every EXT feature)
+template <bool ILVA, bool ILVW>
+int launch_pp_scaled(const mvp_gemm_kscaled* a, hipStream_t s) {
+  static int configured = (int)hipFuncSetAttribute((const void*)gemm_pp_kernel<ILVA, ILVW, false, false, false, mvp_gemm_kscaled>,
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, PP_SMEM);
+  if (configured != 0) return MVP_ELAUNCH;
+  hipLaunchKernelGGL((gemm_pp_kernel<ILVA, ILVW, false, false, false, mvp_gemm_kscaled>), dim3(pp_grid(a)), dim3(512), PP_SMEM, s, *a);
+  MVP_LAUNCH_CHECK();
+  return MVP_OK;
+}
 
-extern "C" int mvp_gemm_pp(const mvp_gemm_args* a, void* stream) {
+// The argument checks of mvp_gemm_pp (both entries)
+int pp_check(const mvp_gemm_args* a) {
   if (!a || !a->a_hi || !a->w_hi) return MVP_EINVAL;
   if (a->pair_layout < 0 || a->pair_layout > (MVP_PAIR_A_ILV32 | MVP_PAIR_W_ILV32)) return MVP_EINVAL;
   const bool ilva = a->pair_layout & MVP_PAIR_A_ILV32, ilvw = a->pair_layout & MVP_PAIR_W_ILV32;
@@ -597,6 +609,15 @@ extern "C" int mvp_gemm_pp(const mvp_gemm_args* a, void* stream) {
   if (a->out_f16_col0 != 0 && ((a->out_f16_col0 != -1 && ((a->out_f16_col0 < 0 ? -a->out_f16_col0 : a->out_f16_col0) & (a->out_f16_col0 < 0 ? 127 : 63))) || !a->out_hi || (!a->out_lo && a->out_pair_layout == MVP_PAIR_SEPARATE))) return MVP_EINVAL;
   // 32-bit per-lane byte offsets: 256 tile rows of the widest supported row must stay below 2 GiB
   if ((int64_t)256 * a->lda * 2 >= 0x7fffff00ll || (int64_t)256 * a->ldw * 2 >= 0x7fffff00ll) return MVP_EINVAL;
+  return MVP_OK;
+}
+
+}  // namespace
+
+extern "C" int mvp_gemm_pp(const mvp_gemm_args* a, void* stream) {
+  if (pp_check(a) != MVP_OK) return MVP_EINVAL;
+  const bool ilva = a->pair_layout & MVP_PAIR_A_ILV32, ilvw = a->pair_layout & MVP_PAIR_W_ILV32;
+  const bool f16x2 = a->precision == MVP_PREC_F16X2;
   hipStream_t st = (hipStream_t)stream;
 #ifdef MVP_PP_ONE  // diagnostic builds: only the interleaved-operand instantiation (fast compiles of experiments)
   return (ilva && ilvw && !a->conv && !f16x2) ? launch_pp<true, true>(a, st) : MVP_EINVAL;
@@ -608,5 +629,22 @@ extern "C" int mvp_gemm_pp(const mvp_gemm_args* a, void* stream) {
   if (a->conv) return ilvw ? launch_pp<false, true, true>(a, st) : launch_pp<false, false, true>(a, st);
   if (ilva) return ilvw ? launch_pp<true, true>(a, st) : launch_pp<true, false>(a, st);
   return ilvw ? launch_pp<false, true>(a, st) : launch_pp<false, false>(a, st);
+#endif
+}
+
+int mvp_gemm_pp_scaled(const mvp_gemm_kscaled* a, void* stream) {
+  if (!a || pp_check(a) != MVP_OK || !a->col_scale || ((size_t)a->col_scale & 15)) return MVP_EINVAL;
+  if (a->conv || a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi) return MVP_EINVAL;
+  const bool ilva = a->pair_layout & MVP_PAIR_A_ILV32, ilvw = a->pair_layout & MVP_PAIR_W_ILV32;
+  hipStream_t st = (hipStream_t)stream;
+#ifdef MVP_PP_ONE
+  return MVP_EINVAL;
+#else
+  if (a->precision == MVP_PREC_F16X2) {
+    if (ilva) return ilvw ? launch_pp_f16x2<true, true>(a, st) : launch_pp_f16x2<true, false>(a, st);
+    return ilvw ? launch_pp_f16x2<false, true>(a, st) : launch_pp_f16x2<false, false>(a, st);
+  }
+  if (ilva) return ilvw ? launch_pp_scaled<true, true>(a, st) : launch_pp_scaled<true, false>(a, st);
+  return ilvw ? launch_pp_scaled<false, true>(a, st) : launch_pp_scaled<false, false>(a, st);
 #endif
 }

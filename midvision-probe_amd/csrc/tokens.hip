@@ -66,12 +66,55 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const mvp_patch_gathe
   }
 }
 
+// Padded form (any P; DINOv2's P = 14 puts a row's 4 consecutive columns across kernel rows and channels, so every element finds its
+// own source pixel): rows of ldk elements, columns [C*P*P, ldk) zero.  A thread writes 4 consecutive columns (Kc % 4 == 0 for every P
+// with C*P*P % 4 == 0, checked on the host, so a group of 4 is either all data or all padding).
+__global__ __launch_bounds__(256) void patch_gather_ld_kernel(const mvp_patch_gather_ld_args pa) {
+  const mvp_patch_gather_args& p = pa.g;
+  const int P = p.P, PP = P * P, Kc = p.C * PP, ld4 = pa.ldk >> 2;
+  const int64_t rows = (int64_t)p.B * p.gh * p.gw;
+  const int64_t total4 = rows * ld4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / ld4;
+    const int col = (int)(i - row * ld4) << 2;
+    const int b = (int)(row / (p.gh * p.gw));
+    const int pr = (int)(row - (int64_t)b * p.gh * p.gw);
+    const int py = pr / p.gw, px = pr - py * p.gw;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (col < Kc) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int k = col + e;
+        const int c = k / PP, rem = k - c * PP, ky = rem / P, kx = rem - ky * P;
+        const int y = py * P + ky - p.pad_top, x = px * P + kx - p.pad_left;
+        if (y >= 0 && y < p.H && x >= 0 && x < p.W) v[e] = p.images[(((size_t)b * p.C + c) * p.H + y) * p.W + x];
+      }
+    }
+    uint16_t h[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) split_bf16(v[e], h[e], l[e]);
+    const size_t o = (size_t)row * pa.ldk + col;
+    *(u32x2_t*)(p.out_hi + o) = u32x2_t{pack2(h[0], h[1]), pack2(h[2], h[3])};
+    if (p.out_lo) *(u32x2_t*)(p.out_lo + o) = u32x2_t{pack2(l[0], l[1]), pack2(l[2], l[3])};
+  }
+}
+
 // ----------------------------------------------------------------------------- cls rows
 __global__ __launch_bounds__(256) void cls_rows_kernel(const mvp_cls_rows_args p) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= p.B * p.C) return;
   const int b = i / p.C, c = i - b * p.C;
   p.x[(size_t)b * p.N * p.C + c] = p.cls[c] + p.pos0[c];
+}
+
+// CLS row + R register rows per image: thread i -> (image, prefix row, column)
+__global__ __launch_bounds__(256) void prefix_rows_kernel(const mvp_prefix_rows_args p) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int per = (1 + p.R) * p.C;
+  if (i >= (int64_t)p.B * per) return;
+  const int b = (int)(i / per), j = (int)(i - (int64_t)b * per);
+  const int r = j / p.C, c = j - r * p.C;
+  p.x[((size_t)b * p.N + r) * p.C + c] = r == 0 ? p.cls[c] + p.pos0[c] : p.reg[(size_t)(r - 1) * p.C + c];
 }
 
 // ----------------------------------------------------------------------------- BN over tokens
@@ -342,6 +385,27 @@ extern "C" int mvp_patch_gather(const mvp_patch_gather_args* a, void* stream) {
   if (a->gh * a->P < a->H + a->pad_top || a->gw * a->P < a->W + a->pad_left) return MVP_EINVAL;
   const int64_t total4 = (int64_t)a->B * a->gh * a->gw * ((a->C * a->P * a->P) >> 2);
   hipLaunchKernelGGL(patch_gather_kernel, dim3(grid_for(total4, 4096)), dim3(256), 0, (hipStream_t)stream, *a);
+  MVP_LAUNCH_CHECK();
+  return MVP_OK;
+}
+
+extern "C" int mvp_patch_gather_ld(const mvp_patch_gather_ld_args* a, void* stream) {
+  if (!a || !a->g.images || !a->g.out_hi) return MVP_EINVAL;
+  const mvp_patch_gather_args& g = a->g;
+  if (g.P <= 0 || g.B <= 0 || g.C <= 0 || g.gh <= 0 || g.gw <= 0 || g.pad_top < 0 || g.pad_left < 0) return MVP_EINVAL;
+  if (((g.C * g.P * g.P) & 3) || (a->ldk & 3) || a->ldk < g.C * g.P * g.P) return MVP_EINVAL;
+  if (g.gh * g.P < g.H + g.pad_top || g.gw * g.P < g.W + g.pad_left) return MVP_EINVAL;
+  if (((size_t)g.out_hi & 7) || ((size_t)g.out_lo & 7)) return MVP_EINVAL;
+  const int64_t total4 = (int64_t)g.B * g.gh * g.gw * (a->ldk >> 2);
+  hipLaunchKernelGGL(patch_gather_ld_kernel, dim3(grid_for(total4, 4096)), dim3(256), 0, (hipStream_t)stream, *a);
+  MVP_LAUNCH_CHECK();
+  return MVP_OK;
+}
+
+extern "C" int mvp_prefix_rows(const mvp_prefix_rows_args* a, void* stream) {
+  if (!a || !a->cls || !a->pos0 || !a->x || a->B <= 0 || a->C <= 0 || a->R < 0 || a->N < 1 + a->R || (a->R > 0 && !a->reg)) return MVP_EINVAL;
+  const int64_t n = (int64_t)a->B * (1 + a->R) * a->C;
+  hipLaunchKernelGGL(prefix_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a);
   MVP_LAUNCH_CHECK();
   return MVP_OK;
 }

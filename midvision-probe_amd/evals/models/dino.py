@@ -1,5 +1,5 @@
 """evals.models.dino.DINO — drop-in for the reference wrapper (evals/models/dino.py:9-210),
-ViT-B/16 dense (multi-layer) feature extraction on the HIP kernels."""
+ViT-B/16 and DINOv2 (ViT-B/14, B/14 with registers, L/14) dense (multi-layer) feature extraction on the HIP kernels."""
 from __future__ import annotations
 
 import warnings
@@ -16,8 +16,14 @@ class DINO(bb.ViTBackbone):
                  weights=None, precision=None, init_seed=0):
         super().__init__()
         feat_dims = {"vitb8": 768, "vitb16": 768, "vitb14": 768, "vitb14_reg": 768, "vitl14": 1024, "vitg14": 1536}
-        if dino_name != "dino" or model_name != "vitb16":
-            raise NotImplementedError("the HIP path covers DINO ViT-B/16 (configs/backbone/dino_b16.yaml)")
+        v2 = dino_name == "dinov2"
+        if v2 and model_name == "vitg14":
+            raise NotImplementedError("dinov2 vitg14: its SwiGLU MLP (C = 1536) has no HIP path; vitb14, vitb14_reg and vitl14 do")
+        if not ((dino_name == "dino" and model_name == "vitb16") or (v2 and model_name in bb.DINOV2_ARCH)):
+            raise NotImplementedError("the HIP path covers DINO ViT-B/16 and DINOv2 ViT-B/14, B/14-reg, L/14 (configs/backbone/dino_b16.yaml, dinov2_*.yaml)")
+        if v2 and return_kqv:
+            # the reference's extract_kqv calls self.vit.prepare_tokens (dino.py:104), which DINOv2's hub model does not have
+            raise NotImplementedError("return_kqv with dinov2: the reference's extract_kqv has no DINOv2 path (prepare_tokens)")
         if return_kqv and mode_selected not in ("k", "q", "v", "kqv"):
             raise ValueError(f"mode_selected {mode_selected!r}: one of k, q, v, kqv (dino.py:126-139)")
         self.arch = "vit"
@@ -28,14 +34,22 @@ class DINO(bb.ViTBackbone):
         # local checkpoint (MVP_CKPT_DIR/<checkpoint_name>.pth) or an explicit state dict, else seeded random init.
         sd = weights
         if sd is None:
-            path = bb.find_checkpoint(self.checkpoint_name, "dino_vitbase16_pretrain")
+            hub = bb.DINOV2_HUB_NAMES[model_name] if v2 else "dino_vitbase16_pretrain"
+            path = bb.find_checkpoint(self.checkpoint_name, hub)
             if path is not None:
                 sd = bb.load_checkpoint_file(path)
             else:
                 warnings.warn(f"no local checkpoint for {self.checkpoint_name}: using seeded random init (seed={init_seed})")
-                sd = bb.random_vit_state_dict(seed=init_seed)
+                if v2:
+                    C, depth, R = bb.DINOV2_ARCH[model_name]
+                    sd = bb.random_dinov2_state_dict(C, depth, R, seed=init_seed)
+                else:
+                    sd = bb.random_vit_state_dict(seed=init_seed)
+        if v2:
+            sd = bb.dinov2_hub_to_engine(sd)
         self.vit = bb.ViTParams(sd).eval()
         self.has_registers = "_reg" in model_name
+        self.n_prefix = 1 + (self.vit.register_tokens.shape[1] if hasattr(self.vit, "register_tokens") else 0)
         self.patch_size = self.vit.patch_embed.proj.weight.shape[-1]
         assert output in ["cls", "gap", "dense", "dense-cls"]
         self.output = output
@@ -46,7 +60,10 @@ class DINO(bb.ViTBackbone):
             feat_dim = feat_dim // 2
         self.batchnorms = nn.ModuleList([nn.BatchNorm1d(feat_dim) for _ in self.multilayers])
         self.return_kqv, self.fixed_size, self.mode_selected = return_kqv, fixed_size, mode_selected
-        self.heads, self.ln_eps, self.pos_embed_mode = self.vit.embed_dim // 64, 1e-6, "dino"
+        # DINOv2's register models resample the pos-embed to the grid size with antialiasing (interpolate_offset 0); the others use the
+        # +0.1 scale nudge, DINO's rule
+        self.heads, self.ln_eps = self.vit.embed_dim // 64, 1e-6
+        self.pos_embed_mode = "dinov2_reg" if (v2 and self.has_registers) else "dino"
         self.set_precision(precision or bb.default_precision())
 
     def forward(self, images):

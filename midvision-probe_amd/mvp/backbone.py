@@ -79,6 +79,65 @@ def random_vit_state_dict(embed_dim=768, depth=12, mlp_ratio=4.0, patch=16, img=
     return sd
 
 
+DINOV2_ARCH = {  # model_name -> (embed_dim, depth, register tokens); heads = embed_dim / 64, patch 14, MLP ratio 4, pos-embed 37 x 37 (518 / 14)
+    "vitb14": (768, 12, 0),
+    "vitb14_reg": (768, 12, 4),
+    "vitl14": (1024, 24, 0),
+}
+DINOV2_HUB_NAMES = {"vitb14": "dinov2_vitb14_pretrain", "vitb14_reg": "dinov2_vitb14_reg4_pretrain", "vitl14": "dinov2_vitl14_pretrain"}
+
+
+def random_dinov2_state_dict(embed_dim=768, depth=12, registers=0, patch=14, pos_grid=37, seed=0, in_chans=3) -> Dict[str, torch.Tensor]:
+    """Seeded random DINOv2 weights in the torch.hub key layout (used when no local checkpoint exists): the ViT statistics of
+    random_vit_state_dict, a pos_grid x pos_grid pos-embed (518 / 14 = 37), random register tokens, LayerScale gammas drawn log-uniform
+    over [1e-6, 1] (trained DINOv2 models keep gammas from ~1e-5 to ~1), plus mask_token and the final norm (loaded, unused here)."""
+    g = torch.Generator().manual_seed(seed)
+
+    def tn(*shape, std=0.02):
+        t = torch.empty(*shape)
+        torch.nn.init.trunc_normal_(t, std=std, a=-2.0 * std / 0.02, b=2.0 * std / 0.02, generator=g)
+        return t
+
+    def gamma():
+        return torch.exp(torch.empty(embed_dim).uniform_(math.log(1e-6), 0.0, generator=g))
+
+    hid = 4 * embed_dim
+    sd = {"cls_token": tn(1, 1, embed_dim), "pos_embed": tn(1, pos_grid * pos_grid + 1, embed_dim), "mask_token": torch.zeros(1, embed_dim)}
+    if registers:
+        sd["register_tokens"] = tn(1, registers, embed_dim, std=0.5)
+    bound = 1.0 / math.sqrt(in_chans * patch * patch)
+    sd["patch_embed.proj.weight"] = (torch.rand(embed_dim, in_chans, patch, patch, generator=g) * 2 - 1) * bound
+    sd["patch_embed.proj.bias"] = (torch.rand(embed_dim, generator=g) * 2 - 1) * bound
+    for i in range(depth):
+        p = f"blocks.{i}."
+        for n in ("norm1", "norm2"):
+            sd[p + n + ".weight"] = 1.0 + 0.1 * torch.randn(embed_dim, generator=g)
+            sd[p + n + ".bias"] = 0.02 * torch.randn(embed_dim, generator=g)
+        sd[p + "attn.qkv.weight"], sd[p + "attn.qkv.bias"] = tn(3 * embed_dim, embed_dim), tn(3 * embed_dim)
+        sd[p + "attn.proj.weight"], sd[p + "attn.proj.bias"] = tn(embed_dim, embed_dim), tn(embed_dim)
+        sd[p + "ls1.gamma"] = gamma()
+        sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"] = tn(hid, embed_dim), tn(hid)
+        sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"] = tn(embed_dim, hid), tn(embed_dim)
+        sd[p + "ls2.gamma"] = gamma()
+    sd["norm.weight"], sd["norm.bias"] = torch.ones(embed_dim), torch.zeros(embed_dim)
+    return sd
+
+
+def dinov2_hub_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A DINOv2 torch.hub state dict -> the keys the engine reads: chunked blocks (``blocks.<chunk>.<i>.``, block_chunks > 0) are
+    flattened to ``blocks.<i>.``; ``mask_token`` (masked pre-training only) and the final ``norm.*`` (not on the tap path,
+    dino.py:176-207) are dropped."""
+    out = {}
+    for k, v in sd.items():
+        if k == "mask_token" or k.startswith("norm."):
+            continue
+        parts = k.split(".")
+        if parts[0] == "blocks" and len(parts) > 3 and parts[1].isdigit() and parts[2].isdigit():
+            k = ".".join(["blocks"] + parts[2:])
+        out[k] = v
+    return out
+
+
 def hf_vitmae_to_fused(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """HF ViTMAEModel keys (embeddings.*, encoder.layer.i.attention.attention.{query,key,value},
     layernorm_before/after, intermediate.dense, output.dense) -> the fused DINO-style layout."""
@@ -202,6 +261,7 @@ class ViTBackbone(nn.Module):
             sd = {k: v for k, v in params.state_dict().items()}
             self._engine_obj = ViTEngine(sd, heads=self.heads, patch=self.patch_size, ln_eps=self.ln_eps, precision=self._precision,
                                          device=dev, pos_embed_mode=self.pos_embed_mode)
+            self.n_prefix = self._engine_obj.n_prefix
             self._engine_sig = sig
         return self._engine_obj
 

@@ -74,6 +74,18 @@ class ClsRowsArgs(C.Structure):
     _fields_ = [("cls", _vp), ("pos0", _vp), ("x", _vp), ("B", _i), ("N", _i), ("C", _i)]
 
 
+class GemmScaledArgs(C.Structure):  # mvp_gemm_scaled_args: LayerScale in the GEMM epilogue (ABI 7 addition)
+    _fields_ = [("gemm", GemmArgs), ("col_scale", _vp)]
+
+
+class PatchGatherLdArgs(C.Structure):  # mvp_patch_gather_ld_args: padded patch rows (ABI 7 addition)
+    _fields_ = [("g", PatchGatherArgs), ("ldk", _i)]
+
+
+class PrefixRowsArgs(C.Structure):  # mvp_prefix_rows_args: CLS + register rows (ABI 7 addition)
+    _fields_ = [("cls", _vp), ("pos0", _vp), ("reg", _vp), ("x", _vp), ("B", _i), ("N", _i), ("C", _i), ("R", _i)]
+
+
 class BnTokensArgs(C.Structure):
     _fields_ = [("x", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("stats", _vp),
                 ("nchw", _vp), ("tok_hi", _vp), ("tok_lo", _vp), ("ld_tok", _i), ("col_off", _i),
@@ -254,7 +266,13 @@ SYMBOLS = {
     "mvp_gemm_pp": GemmArgs,
     "mvp_gemm_tn_workspace_bytes": None,
     "mvp_gemm_tn_conv": GemmTnArgs,
+    "mvp_gemm_scaled": GemmScaledArgs,
+    "mvp_patch_gather_ld": PatchGatherLdArgs,
+    "mvp_prefix_rows": PrefixRowsArgs,
 }
+
+# the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
+NEW_STRUCTS_ABI7 = {"mvp_gemm_scaled_args": GemmScaledArgs, "mvp_patch_gather_ld_args": PatchGatherLdArgs, "mvp_prefix_rows_args": PrefixRowsArgs}
 
 _lib: Optional[C.CDLL] = None
 

@@ -161,6 +161,14 @@ def patch_gather(images: torch.Tensor, out: Pair, P: int, gh: int, gw: int, pad_
     lib.call("mvp_patch_gather", a)
 
 
+def patch_gather_ld(images: torch.Tensor, out: Pair, P: int, gh: int, gw: int, pad_top: int, pad_left: int, ldk: int) -> None:
+    """``patch_gather`` into rows of ``ldk`` >= C*P*P elements with zeroed tail columns, any P (mvp_patch_gather_ld: DINOv2's P = 14)."""
+    _chk(images, torch.float32, "patch_gather_ld.images")
+    B, Cc, H, W = images.shape
+    g = lib.PatchGatherArgs(lib.ptr(images), lib.ptr(out[0]), lib.ptr(out[1]), B, Cc, H, W, P, gh, gw, pad_top, pad_left)
+    lib.call("mvp_patch_gather_ld", lib.PatchGatherLdArgs(g, int(ldk)))
+
+
 _SPLITK_WS = {}  # (device, stream) -> zero-initialised workspace (tile counters reset themselves)
 
 
@@ -222,8 +230,10 @@ def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, 
          act: int = lib.ACT_NONE, precision: int = PREC_BF16X3, lda=None, ldw=None, ldr=None, ldo=None, ldob=None,
          row_group=0, row_group_stride=0, row_group_off=0, res_row_mod=0, act_after_res=False, out_mask=None, ldm=0,
          splitk: Optional[int] = None, residual_pair: Optional[Pair] = None, streamk: Optional[bool] = None,
-         w_ilv: Optional[torch.Tensor] = None, f16_col0: int = 0) -> None:
-    """Y = act(A Wᵀ + bias) + residual (see mvp_gemm_bias_act_res).  splitk: None = automatic, 1 = off.
+         w_ilv: Optional[torch.Tensor] = None, f16_col0: int = 0, col_scale: Optional[torch.Tensor] = None) -> None:
+    """Y = act(A Wᵀ + bias) + residual (see mvp_gemm_bias_act_res).
+    col_scale: fp32 [N] LayerScale vector: Y = col_scale * act(A Wᵀ + bias) + residual in the epilogue (mvp_gemm_scaled; never split-K or
+    stream-K, which do not take a scale).  splitk: None = automatic, 1 = off.
     f16_col0 > 0: columns from there on of the pair output are written as hi = fp16, lo = bf16 (mvp_gemm_args.out_f16_col0: the V
     third of the fused qkv projection for ``attention(..., v_f16=True)``); f16_col0 = -1: EVERY column as the activation operand of a
     PREC_F16X2 GEMM (``split_f16_comp``'s form: fc1 -> fc2); no split-K / stream-K either way.
@@ -251,6 +261,9 @@ def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, 
         splitk, streamk = 1, False
     if precision == lib.PREC_F16X2:  # two products per contraction: plain linear GEMMs, no split-K / stream-K (mvp_hip.h)
         splitk, streamk = 1, False
+    if col_scale is not None:
+        _chk(col_scale, torch.float32, "gemm.col_scale")
+        splitk, streamk = 1, False
     if out_mask is not None:
         args.out_mask, args.ldm = lib.ptr(out_mask), ldm or N
     if residual_pair is not None:
@@ -274,12 +287,16 @@ def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, 
     if w_ilv is not None and plain and not use_sk and S <= 1 and tile.startswith("pp ") and ldw is None:
         args.w_hi, args.w_lo, args.ldw = lib.ptr(w_ilv), None, 2 * K
         args.pair_layout |= lib.PAIR_W_ILV32
+    if col_scale is not None:
+        name, args = "mvp_gemm_scaled", lib.GemmScaledArgs(args, lib.ptr(col_scale))
+    else:
+        name = "mvp_gemm_bias_act_res"
     if _TRACE is None:
-        lib.call("mvp_gemm_bias_act_res", args)
+        lib.call(name, args)
         return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    lib.call("mvp_gemm_bias_act_res", args)
+    lib.call(name, args)
     e1.record()
     _TRACE.append(("gemm", "streamk 128, 128, 64" if use_sk else tile, precision, 2.0 * M * N * K, e0, e1))
 
@@ -323,6 +340,12 @@ def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precis
 
 def cls_rows(cls: torch.Tensor, pos0: torch.Tensor, x: torch.Tensor, B: int, N: int, Cdim: int) -> None:
     lib.call("mvp_cls_rows", lib.ClsRowsArgs(lib.ptr(cls), lib.ptr(pos0), lib.ptr(x), B, N, Cdim))
+
+
+def prefix_rows(cls: torch.Tensor, pos0: torch.Tensor, reg: Optional[torch.Tensor], x: torch.Tensor, B: int, N: int, Cdim: int) -> None:
+    """x[b, 0] = cls + pos0 and x[b, 1 + r] = reg[r] (register tokens, no position embedding) in one launch (mvp_prefix_rows)."""
+    R = 0 if reg is None else int(reg.shape[0])
+    lib.call("mvp_prefix_rows", lib.PrefixRowsArgs(lib.ptr(cls), lib.ptr(pos0), lib.ptr(reg), lib.ptr(x), B, N, Cdim, R))
 
 
 def bn_tokens_workspace_bytes(M: int, Cdim: int) -> int:

@@ -171,12 +171,13 @@ def default_depth(probe=None, group: int = 1) -> int:
     return 2 if group > 1 else 4
 
 
-def rows_per_image(H: int, W: int, P: int) -> int:
+def rows_per_image(H: int, W: int, P: int, prefix: int = 1) -> int:
     """Token rows of one image, with the grid ViTEngine.tokens() builds: when either dimension is ragged against the patch size,
-    center_padding pads BOTH by ``P - dim % P`` — a full extra patch for the dimension that was not ragged (utils.py:55-72)."""
+    center_padding pads BOTH by ``P - dim % P`` — a full extra patch for the dimension that was not ragged (utils.py:55-72).
+    ``prefix``: rows in front of the patch rows (CLS + register tokens: ViTEngine.n_prefix)."""
     rh, rw = H % P, W % P
     ph, pw = (0, 0) if (rh == 0 and rw == 0) else (P - rh, P - rw)
-    return 1 + ((H + ph) // P) * ((W + pw) // P)
+    return prefix + ((H + ph) // P) * ((W + pw) // P)
 
 
 GROUP_ROWS = 19000  # token rows a grouped forward aims at: 6 batches of 16 x 197 = 18912 rows = 74 x {3, 9, 12} tiles of 256^2, 87 % of whole rounds of 256 CUs
@@ -194,7 +195,7 @@ def default_group(model, images: torch.Tensor, depth: int) -> int:
         return max(1, min(MAX_GROUP, int(env)))
     P = int(getattr(model, "patch_size", 16))
     B, H, W = images.shape[0], images.shape[-2], images.shape[-1]
-    rows = B * rows_per_image(H, W, P)
+    rows = B * rows_per_image(H, W, P, int(getattr(model, "n_prefix", 1)))
     return max(1, min(MAX_GROUP, int(round(GROUP_ROWS / rows))))
 
 
@@ -224,7 +225,7 @@ def default_span(model, images: torch.Tensor, depth: int, group: int) -> int:
             return 0
         P = int(getattr(model, "patch_size", 16))
         H, W = images.shape[-2], images.shape[-1]
-        rows = rows_per_image(H, W, P)
+        rows = rows_per_image(H, W, P, int(getattr(eng, "n_prefix", 1)))
         unit = max(1, B // 8)
         T = min(((_cu_count() // (-(-C // 256))) * 256) // rows, MAX_GROUP * B) // unit * unit
     return T if (T > B and T % B) else 0

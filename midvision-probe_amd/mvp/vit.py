@@ -2,7 +2,11 @@
 share this engine; the wrappers under evals/models differ in weights, pos-embed policy,
 LayerNorm eps and which block outputs are tapped).
 
-Data layout in HBM (per batch of B images, N = 1 + gh*gw tokens, M = B*N rows):
+DINOv2 (ViT-B/14, B/14 with registers, L/14) runs on the same engine: R register tokens follow the CLS row (n_prefix = 1 + R prefix
+rows per image, written by mvp_prefix_rows), LayerScale vectors (blocks.i.ls1.gamma / ls2.gamma) are applied in the proj / fc2 epilogues
+(mvp_gemm_scaled), and the 14x14 patches are gathered into zero-padded rows (mvp_patch_gather_ld) against zero-padded weights.
+
+Data layout in HBM (per batch of B images, N = n_prefix + gh*gw tokens, n_prefix = 1 + R, M = B*N rows):
   x        fp32  [M, C]      residual stream (kept fp32: LN statistics and residual adds)
   xn       bf16 pair [M, C]  LayerNorm output = A operand of the next GEMM
   qkv      bf16 pair [M, 3C] fused projection, read in place by the attention kernel
@@ -121,6 +125,10 @@ def lookup_pack(maps: Sequence[torch.Tensor]) -> Optional[PackedFeatures]:
 class ViTEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, heads: int, patch: int = 16, ln_eps: float = 1e-6,
                  precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True):
+        """``state_dict`` in the DINO / timm layout; DINOv2's extras are picked up from it: ``register_tokens`` [1, R, C] (then
+        n_prefix = 1 + R) and ``blocks.i.ls1.gamma`` / ``blocks.i.ls2.gamma`` (LayerScale, fused into the proj / fc2 epilogues).
+        pos_embed_mode: 'dino' (bicubic with the +0.1 scale nudge), 'fixed', or 'dinov2_reg' (bicubic to the grid size, antialiased:
+        DINOv2's register models)."""
         self.device = torch.device(device)
         self.precision = parse_precision(precision)
         # 'f16x2': a bf16x3 engine (buffers, patch embedding, attention, taps) whose four block GEMMs run two products (lib.PREC_F16X2)
@@ -144,9 +152,20 @@ class ViTEngine:
         self.depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
         self.cls = sd["cls_token"].reshape(-1).contiguous()
         self.pos_embed = sd["pos_embed"]  # [1, 1+n, C] fp32
+        reg = sd.get("register_tokens")
+        self.reg = reg.reshape(-1, self.C).contiguous() if reg is not None and reg.numel() else None  # [R, C]
+        self.n_prefix = 1 + (0 if self.reg is None else self.reg.shape[0])
         pw = sd["patch_embed.proj.weight"]
         self.in_chans = pw.shape[1]
-        self.w_patch = ops.split_bf16(pw.reshape(self.C, -1), self.precision)
+        # patch-embed GEMM depth: C*P*P, padded with zero columns to what the tile kernels take (K % 32 in bf16x3, else K % 64) when the
+        # patch is not a multiple of 4 or the depth is not aligned (P = 14: 588 -> 608); the gather then writes zero tails (mvp_patch_gather_ld)
+        kp = pw[0].numel()
+        q = 32 if self.precision == PREC_BF16X3 else 64
+        self.k_patch = kp if (kp % q == 0 and patch % 4 == 0) else -(-kp // q) * q
+        pw2 = pw.reshape(self.C, -1)
+        if self.k_patch != kp:
+            pw2 = F.pad(pw2, (0, self.k_patch - kp)).contiguous()
+        self.w_patch = ops.split_bf16(pw2, self.precision)
         self.b_patch = sd["patch_embed.proj.bias"]
         self.blocks = []
         for i in range(self.depth):
@@ -159,6 +178,7 @@ class ViTEngine:
                 n2w=sd[p + "norm2.weight"], n2b=sd[p + "norm2.bias"],
                 fc1_w=ops.split_bf16(sd[p + "mlp.fc1.weight"], self.precision), fc1_b=sd[p + "mlp.fc1.bias"],
                 fc2_w=ops.split_bf16(sd[p + "mlp.fc2.weight"], self.precision), fc2_b=sd[p + "mlp.fc2.bias"],
+                ls1=sd.get(p + "ls1.gamma"), ls2=sd.get(p + "ls2.gamma"),  # LayerScale (DINOv2) or None
             )
             if self.f16x2:  # the weight operands of the two-product GEMMs (ops.f16x2_weight: compensated fp16 pairs)
                 for n in ("qkv_w", "proj_w", "fc1_w", "fc2_w"):
@@ -204,7 +224,7 @@ class ViTEngine:
         if ws is not None and ws["headroom"] < headroom:
             ws = None
         if ws is None:
-            N = 1 + gh * gw
+            N = self.n_prefix + gh * gw
             M = B * N
             C, dev, pr = self.C, self.device, self.precision
             # When every GEMM of a block goes to the large-M kernel (M fills whole rounds of 256x256 tiles: grouped forwards), its A
@@ -219,7 +239,7 @@ class ViTEngine:
                 qkv=ops.empty_pair((M, 3 * C), pr, dev),
                 ao=ops.IlvPair(M, C, dev) if ilv else ops.empty_pair((M, C), pr, dev),
                 hmid=ops.IlvPair(M, self.hidden, dev) if ilv else ops.empty_pair((M, self.hidden), pr, dev),
-                patches=ops.empty_pair((B * gh * gw, self.in_chans * self.patch * self.patch), pr, dev),
+                patches=ops.empty_pair((B * gh * gw, self.k_patch), pr, dev),
             )
             self._ws = {k: v for k, v in self._ws.items() if k[:3] == key[:3]}  # keep one resolution resident (one buffer set per slot)
             self._ws[key] = ws
@@ -243,6 +263,11 @@ class ViTEngine:
         n = self.pos_embed.shape[1] - 1
         if self.pos_embed_mode == "fixed" or (gh * gw == n and dim2 == dim3):
             pe = self.pos_embed[0].contiguous()
+        elif self.pos_embed_mode == "dinov2_reg":  # DINOv2 register models: interpolate_offset 0, antialias (size = the grid)
+            side = int(math.sqrt(n))
+            grid = self.pos_embed[:, 1:].reshape(1, side, side, self.C).permute(0, 3, 1, 2)
+            grid = F.interpolate(grid, size=(dim2 // self.patch, dim3 // self.patch), mode="bicubic", antialias=True)
+            pe = torch.cat((self.pos_embed[0, :1], grid.permute(0, 2, 3, 1).reshape(-1, self.C)), dim=0).contiguous()
         else:
             side = int(math.sqrt(n))
             w0, h0 = dim2 // self.patch + 0.1, dim3 // self.patch + 0.1
@@ -272,14 +297,21 @@ class ViTEngine:
             ph, pw = P - rh, P - rw
         gh, gw = (H + ph) // P, (W + pw) // P
         ws = self._workspace(B, gh, gw, headroom)
-        N, C = 1 + gh * gw, self.C
-        ops.patch_gather(images, ws["patches"], P, gh, gw, ph // 2, pw // 2)
+        npre, C = self.n_prefix, self.C
+        N = npre + gh * gw
+        Kp = self.k_patch
+        if Kp == Cin * P * P:
+            ops.patch_gather(images, ws["patches"], P, gh, gw, ph // 2, pw // 2)
+        else:
+            ops.patch_gather_ld(images, ws["patches"], P, gh, gw, ph // 2, pw // 2, Kp)
         pos = self.pos_for(gh, gw, H + ph, W + pw)
-        Kp = Cin * P * P
-        # x[b, 1+p, :] = patches · Wᵀ + bias + pos[1+p]   (row remap skips the CLS slot)
+        # x[b, npre+p, :] = patches · Wᵀ + bias + pos[1+p]   (row remap skips the CLS / register slots)
         ops.gemm(ws["patches"], self.w_patch, B * gh * gw, C, Kp, bias=self.b_patch, residual=pos[1:], out_f32=ws["x"],
-                 precision=self.precision, row_group=gh * gw, row_group_stride=N, row_group_off=1, res_row_mod=gh * gw)
-        ops.cls_rows(self.cls, pos, ws["x"], B, N, C)
+                 precision=self.precision, row_group=gh * gw, row_group_stride=N, row_group_off=npre, res_row_mod=gh * gw)
+        if self.reg is None:
+            ops.cls_rows(self.cls, pos, ws["x"], B, N, C)
+        else:
+            ops.prefix_rows(self.cls, pos, self.reg, ws["x"], B, N, C)
         return ws, B, gh, gw
 
     def _check_f16_range(self, what: str, pair, rows: int) -> None:
@@ -311,7 +343,8 @@ class ViTEngine:
         ops.attention(ws["qkv"], ws["ao"], B, N, self.heads, 64 ** -0.5, pr, v_f16=vf16, qk_f16=qk16, out_f16=f2)
         if chk:
             self._check_f16_range(f"block {i}: attention output", ws["ao"], M)
-        ops.gemm(ws["ao"], blk["proj_w"], M, C, C, bias=blk["proj_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("proj_w_ilv"))
+        ops.gemm(ws["ao"], blk["proj_w"], M, C, C, bias=blk["proj_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("proj_w_ilv"),
+                 col_scale=blk["ls1"])
         ops.layernorm(x, blk["n2w"], blk["n2b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
         if chk:
             self._check_f16_range(f"block {i}: LayerNorm 2 output", ws["xn"], M)
@@ -319,7 +352,8 @@ class ViTEngine:
                  f16_col0=-1 if f2 else 0)
         if chk:
             self._check_f16_range(f"block {i}: GELU(fc1) output", ws["hmid"], M)
-        ops.gemm(ws["hmid"], blk["fc2_w"], M, C, self.hidden, bias=blk["fc2_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("fc2_w_ilv"))
+        ops.gemm(ws["hmid"], blk["fc2_w"], M, C, self.hidden, bias=blk["fc2_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("fc2_w_ilv"),
+                 col_scale=blk["ls2"])
 
     def forward_taps(self, images: torch.Tensor, layers: Sequence[int], *, bn: Optional[Sequence[dict]] = None,
                      bn_mode: int = 0, pack: bool = True, tap_input_of_block: bool = False, want_cls: bool = False, groups: int = 1):
@@ -341,7 +375,7 @@ class ViTEngine:
         (carry + images) // batch batches this forward completes."""
         span = groups if isinstance(groups, pipeline.Span) else None
         ws, Bt, gh, gw = self.tokens(images, headroom=span.batch if span else 0)
-        N, C, hw = 1 + gh * gw, self.C, gh * gw
+        N, C, hw = self.n_prefix + gh * gw, self.C, gh * gw
         if span is not None:
             B, carry = int(span.batch), int(span.carry)
             if B < 1 or not 0 <= carry < B:
@@ -459,7 +493,7 @@ class ViTEngine:
         with a forward hook on ``blocks[-1].attn.qkv`` (dino.py:82-113).  Blocks 0 .. depth-2 run as usual; the last block stops after
         LayerNorm 1 and the projection (its attention output is never used on that path)."""
         ws, B, gh, gw = self.tokens(images)
-        N = 1 + gh * gw
+        N = self.n_prefix + gh * gw
         for i in range(self.depth - 1):
             self.run_block(i, ws, B, N)
         blk, C, M = self.blocks[self.depth - 1], self.C, B * N
@@ -473,7 +507,7 @@ class ViTEngine:
     def forward_tokens(self, images: torch.Tensor, n_blocks: Optional[int] = None) -> torch.Tensor:
         """Raw fp32 token stream after ``n_blocks`` blocks ([B, N, C]); for tests / CLS outputs."""
         ws, B, gh, gw = self.tokens(images)
-        N = 1 + gh * gw
+        N = self.n_prefix + gh * gw
         for i in range(self.depth if n_blocks is None else n_blocks):
             self.run_block(i, ws, B, N)
         return ws["x"].view(B, N, self.C).clone()

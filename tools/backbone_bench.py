@@ -1,0 +1,106 @@
+"""The driver's training step for several ViT backbones side by side: B images at 224^2 (synthetic NYU-shaped batches resident in HBM), the
+backbone with return_multilayer (4 taps, train-mode tap BN) -> DepthHead(linear, k = 1, bindepth) -> bilinear -> DepthLoss -> backward ->
+FlatAdamW, PIPELINED as train_depth.py runs it (mvp.pipeline: the trainers' default in-flight depth, grouped / span forwards, hipGraph
+replay), backbone precision f16x2.  Models: dino_b16 (bench.py's headline), dinov2_b14, dinov2_b14_reg, dinov2_l14 (seeded weights), in
+one process, alternating round by round so that clock and thermal drift hit all of them alike.  Each round = STEPS steps between two
+barriers (the pipeline starts and ends empty), after WARMUP untimed steps per model (graph capture).
+
+    python tools/backbone_bench.py [--batch 16] [--rounds 5] [--steps 30] [--warmup 8] [--models dino_b16,dinov2_b14,...]
+
+One line per model: median img/s over the rounds, the ratio to dino_b16, the pipeline's shape."""
+from __future__ import annotations
+
+import argparse
+import os
+import statistics
+import subprocess
+import sys
+import time
+import warnings
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "midvision-probe_amd")]
+
+import torch  # noqa: E402
+
+MODELS = {"dino_b16": ("dino", "vitb16", "dense"), "dinov2_b14": ("dinov2", "vitb14", "dense-cls"),
+          "dinov2_b14_reg": ("dinov2", "vitb14_reg", "dense-cls"), "dinov2_l14": ("dinov2", "vitl14", "dense-cls")}
+
+
+def build(name, precision, dev):
+    from evals.models.dino import DINO
+    from evals.models.probes import DepthHead
+    from evals.utils.optim import cosine_decay_linear_warmup
+    from mvp.optim import FlatAdamW
+
+    dn, mn, out = MODELS[name]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # seeded random init
+        model = DINO(dino_name=dn, model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
+    torch.manual_seed(0)
+    probe = DepthHead(feat_dim=model.feat_dim, head_type="linear", kernel_size=1, prediction_type="bindepth", min_depth=0.001, max_depth=10).to(dev)
+    opt = FlatAdamW([{"params": probe.parameters(), "lr": 5e-4}])
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda e: cosine_decay_linear_warmup(e, 100000, 100))
+    return model, probe, opt, sched
+
+
+def main():
+    from evals.utils.losses import DepthLoss
+    from mvp.pipeline import pipelined_features
+    from mvp.train import train_depth_step
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--precision", default="f16x2")
+    ap.add_argument("--models", default=",".join(MODELS))
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B, H, W = a.batch, 224, 224
+    names = a.models.split(",")
+    batches = []
+    for s in range(4):
+        g = torch.Generator().manual_seed(1000 + s)
+        depth = torch.rand(B, 1, H, W, generator=g) * 9.9 + 0.05
+        depth[torch.rand(B, 1, H, W, generator=g) < 0.1] = 0.0
+        batches.append({"image": torch.randn(B, 3, H, W, generator=g).to(dev), "depth": depth.to(dev)})
+    runs = {n: build(n, a.precision, dev) for n in names}
+    loss_fn = DepthLoss()
+
+    def steps(name, n):
+        model, probe, opt, sched = runs[name]
+        seq = [batches[i % len(batches)] for i in range(n)]
+        for b, f in pipelined_features(model, seq, probe=probe):
+            train_depth_step(model, probe, opt, sched, loss_fn, None, b["depth"], feats=f)
+        opt.finish_pending()
+        torch.cuda.synchronize()
+
+    for n in names:
+        steps(n, a.warmup)
+    rates = {n: [] for n in names}
+    for _ in range(a.rounds):
+        for n in names:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            steps(n, a.steps)
+            rates[n].append(B * a.steps / (time.perf_counter() - t0))
+    try:
+        rev = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or "n/a"
+    except OSError:
+        rev = "n/a"
+    print(f"# tools/backbone_bench.py  B={B} {H}x{W} {a.precision} linear k=1 bindepth probe, pipelined; {a.rounds} rounds x {a.steps} steps "
+          f"(+{a.warmup} warm-up); tree {rev}; {time.strftime('%Y-%m-%d')}")
+    base = statistics.median(rates[names[0]])
+    from mvp.pipeline import cached_pipelines
+
+    for n in names:
+        r = statistics.median(rates[n])
+        pipes = [p for p in cached_pipelines(runs[n][0]).values()]
+        shape = f"depth={pipes[0].depth} group={pipes[0].group} span={pipes[0].span}" if pipes else ""
+        print(f"{n:16s} {r:8.0f} img/s  ({r / base:.2f}x {names[0]}; {shape}; rounds {', '.join(f'{x:.0f}' for x in rates[n])})")
+
+
+if __name__ == "__main__":
+    main()
