@@ -63,7 +63,11 @@ typedef struct {
   int cu_count;         /* multiProcessorCount of device 0                   */
   char arch[64];        /* gcnArchName of device 0                           */
 } mvp_info_t;
-#define MVP_ABI_VERSION 7 /* 7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
+#define MVP_ABI_VERSION 8 /* 8: two exports removed, one added.  Removed: the round-2 k-balanced GEMM (its launch and workspace query; slower than
+                                the tile kernels on every shape measured), so splitk < 0 is now MVP_EINVAL.  Added: mvp_gemm_route
+                                (and its struct mvp_gemm_route_t, tagged like the later additions within 7), which reports the kernel
+                                mvp_gemm_bias_act_res would run.  Every other struct, mvp_gemm_args included, as in 7.
+                             7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
                                 their argument structs are tagged structs (struct X {...}; typedef'd ahead), the ABI 7 set of `} mvp_*;` structs is unchanged
@@ -155,9 +159,7 @@ typedef struct {
    * with too few output tiles to fill 256 CUs (N = 768 projections, the probe head at M ~ 3k rows).
    * splitk_ws: >= mvp_gemm_splitk_workspace_bytes(M, N, splitk) bytes whose leading tile counters are ZERO
    * at first use (they reset themselves); not shared by GEMMs running concurrently on other streams.
-   * splitk == MVP_GEMM_STREAMK (-1): stream-K scheduling instead (csrc/gemm_sk.hip): one workgroup per CU, every CU gets the
-   * same number of k-iterations of 128x128x64 tiles whatever the tile count; same bit-reproducible fixed-order reduction of
-   * partial tiles; splitk_ws >= mvp_gemm_streamk_workspace_bytes(), 16-byte aligned, counters ZERO at first use.        */
+   * splitk 0 or 1: no split; splitk < 0: MVP_EINVAL.                                                                  */
   int splitk; void* splitk_ws; int64_t splitk_ws_bytes;
   /* --- optional residual given as a bf16 pair (row stride ldr, elements), added like `residual`:
    * lets a frozen trunk keep block outputs only as pairs (ResNet identities, dino_res50.py:83-101). */
@@ -185,7 +187,7 @@ typedef struct {
    * out_f16_col0 > 0 (a multiple of 64): columns >= out_f16_col0 are written as hi = fp16(v) (round to nearest even), lo = bf16(v - hi) instead of
    * hi = bf16(v), lo = bf16(v - hi) — the V third of the fused qkv projection (out_f16_col0 = 2 * H * 64), which the attention
    * kernel multiplies with probabilities held as ONE fp16 value (mvp_attention_args.v_format).  Same 2 + 2 bytes, same arrays and
-   * layouts; |v - hi - lo| <= 2^-20 |v|.  Every kernel of mvp_gemm_bias_act_res / mvp_gemm_pp writes it (not stream-K).
+   * layouts; |v - hi - lo| <= 2^-20 |v|.  Every kernel of mvp_gemm_bias_act_res / mvp_gemm_pp writes it.
    * out_f16_col0 = -V0 < -1 (ABI 7; V0 a multiple of 128 = the first column of the V third, 2 * H * 64): the fused qkv projection for
    * MVP_ATT_V_F16_QK_F16 — columns [0, V0 / 2) (Q) as the compensated activation pair, [V0 / 2, V0) (K) as the compensated WEIGHT-side pair
    * (hi = fp16((1 - 2^-6) v), lo = fp16((v + 64 d) / 8), d = (1 - 2^-6) v - hi, fp32 arithmetic; hi + lo / 8 = v to ~2^-17), [V0, N) (V) as above. */
@@ -195,7 +197,6 @@ typedef struct {
 #define MVP_TILES_SHARED 1
 #define MVP_TILES_NO_PP 2 /* flag, or-ed in: never dispatch to the large-M kernel mvp_gemm_pp (A/B measurements, tests of the tile kernels) */
 #define MVP_TILES_NO_UNI 4 /* flag, or-ed in: keep the row-guarded epilogue where the universal branch-free one (gemm_epilogue_uni) would serve (A/B, bit-identity tests) */
-#define MVP_GEMM_STREAMK (-1)
 #define MVP_PAIR_SEPARATE 0
 #define MVP_PAIR_A_ILV32 1
 #define MVP_PAIR_W_ILV32 2
@@ -208,12 +209,26 @@ int mvp_gemm_bias_act_res(const mvp_gemm_args*, void* stream);
  * this entry point forces it (benchmarks, tests).  Replaces the same nn.Linear call sites (ibot_transformers.py:95-106,124-145). */
 int mvp_gemm_pp(const mvp_gemm_args*, void* stream);
 int64_t mvp_gemm_splitk_workspace_bytes(int M, int N, int splits);
-int64_t mvp_gemm_streamk_workspace_bytes(void);
-int mvp_gemm_streamk(const mvp_gemm_args*, void* stream);  /* what mvp_gemm_bias_act_res dispatches to for splitk == MVP_GEMM_STREAMK */
+/* (ABI 8) Which kernel mvp_gemm_bias_act_res runs for these arguments — the library's one rule, csrc/gemm.hip — and the template
+ * arguments of that instantiation.  Host only: touches no device, reads no operand (pointers are only tested for NULL).  Returns what
+ * mvp_gemm_bias_act_res would return, MVP_OK or MVP_EINVAL, except that the split-K workspace is not checked.  mvp_gemm_scaled routes
+ * its `gemm` part the same way.                                                                                                  */
+#define MVP_GEMM_ROUTE_PP 1     /* the large-M kernel (mvp_gemm_pp): bm, bn, bk = 256, 256, 32, and split; nstage, nw, wnw are 0  */
+#define MVP_GEMM_ROUTE_TILE 2   /* a tile kernel                                                                                 */
+#define MVP_GEMM_ROUTE_SPLITK 3 /* a tile kernel with split-K (splitk > 1)                                                       */
+#define MVP_GEMM_ROUTE_CONV 4   /* a tile kernel of the implicit-GEMM convolution (conv != 0)                                    */
+typedef struct mvp_gemm_route_t mvp_gemm_route_t;
+struct mvp_gemm_route_t {
+  int family;           /* MVP_GEMM_ROUTE_*                                                                   */
+  int bm, bn, bk;       /* output tile, k-depth of one LDS stage                                              */
+  int split;            /* products per contraction: 1 (MVP_PREC_BF16), 3 (MVP_PREC_BF16X3), 2 (MVP_PREC_F16X2) */
+  int nstage, nw, wnw;  /* LDS stages, waves per workgroup, waves along N                                     */
+};
+int mvp_gemm_route(const mvp_gemm_args*, mvp_gemm_route_t* out);
 /* LayerScale fused into the epilogue (DINOv2 blocks: x + ls1.gamma * proj(.), x + ls2.gamma * fc2(.)):
  *   Y[m, n] = col_scale[n] * act(A · Wᵀ + bias)[m, n] + residual
  * i.e. the scale is applied after bias and activation, before the residual add.  `gemm` keeps mvp_gemm_bias_act_res's contract and
- * tile / large-M dispatch (both pair layouts, every precision); not supported (MVP_EINVAL): convolutions, split-K, stream-K, masks,
+ * tile / large-M dispatch (both pair layouts, every precision); not supported (MVP_EINVAL): convolutions, split-K, masks,
  * pair residuals, residual2, act_after_res.  The scale is NOT folded into the weights: a tiny gamma (1e-5) would push the fp16 halves
  * of the MVP_PREC_F16X2 weight pairs into subnormals.  col_scale: [N] fp32, 16-byte aligned.                                       */
 typedef struct mvp_gemm_scaled_args mvp_gemm_scaled_args;

@@ -439,15 +439,42 @@ int launch_gemm_splitk(const mvp_gemm_args* a, hipStream_t s) {
 // One tile rule for the split-K path (the workspace query must agree with the launch).
 inline bool splitk_wide(int N) { return N >= 1024; }
 
+// A route = what mvp_gemm_route reports + the launcher of the instantiation it names (launch_scaled: the same instantiation with the
+// LayerScale epilogue, for mvp_gemm_scaled; NULL for the convolution and split-K tiles, which have none).
+struct Route {
+  mvp_gemm_route_t r;
+  int (*launch)(const mvp_gemm_args*, hipStream_t);
+  int (*launch_scaled)(const mvp_gemm_kscaled*, hipStream_t);
+};
+
+template <int BM, int BN, int BK, int SPLIT, int NSTAGE, bool CONV = false, int NW = 4, int WNW = 2>
+int route_tile(Route* o) {
+  *o = {{CONV ? MVP_GEMM_ROUTE_CONV : MVP_GEMM_ROUTE_TILE, BM, BN, BK, SPLIT, NSTAGE, NW, WNW}, launch_gemm<BM, BN, BK, SPLIT, NSTAGE, CONV, NW, WNW>, nullptr};
+  if constexpr (!CONV) o->launch_scaled = launch_gemm<BM, BN, BK, SPLIT, NSTAGE, false, NW, WNW, mvp_gemm_kscaled>;
+  return MVP_OK;
+}
+
+template <int BM, int BN, int BK, int SPLIT, int NSTAGE>
+int route_splitk(Route* o) {
+  *o = {{MVP_GEMM_ROUTE_SPLITK, BM, BN, BK, SPLIT, NSTAGE, 4, 2}, launch_gemm_splitk<BM, BN, BK, SPLIT, NSTAGE>, nullptr};
+  return MVP_OK;
+}
+
+// "The large-M kernel" means that mvp_gemm_pp accepts the arguments: its checks run here
+int route_pp(const mvp_gemm_args* a, Route* o) {
+  if (pp_check(a) != MVP_OK) return MVP_EINVAL;
+  *o = {{MVP_GEMM_ROUTE_PP, 256, 256, 32, a->precision == MVP_PREC_F16X2 ? 2 : 3, 0, 0, 0},
+        [](const mvp_gemm_args* g, hipStream_t s) { return mvp_gemm_pp(g, s); },
+        [](const mvp_gemm_kscaled* g, hipStream_t s) { return mvp_gemm_pp_scaled(g, s); }};
+  return MVP_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t mvp_gemm_splitk_workspace_bytes(int M, int N, int splits) {
   if (M <= 0 || N <= 0 || splits < 1) return 0;
   return splitk_wide(N) ? splitk_ws_bytes<128, 128>(M, N, splits) : splitk_ws_bytes<128, 64>(M, N, splits);
 }
-
-// Diagnostic override (tools/gemm_bench.py): -DMVP_F_BM=.. -DMVP_F_BN=.. -DMVP_F_BK=.. -DMVP_F_ST=..
-extern "C" int mvp_gemm_streamk(const mvp_gemm_args* a, void* stream);  // gemm_sk.hip
 
 // When the large-M kernel (gemm_pp.hip: 256x256 tiles, one workgroup per CU) takes a plain bf16x3 GEMM.  Measured on MI355X
 // (tools/pp_bench.py, us, tile kernel -> pp; M = 197 * B): B = 16 (39-117 tiles of 256^2): 38.7 -> 53.7 (qkv), 63.4 -> 154.9 (fc2): never;
@@ -485,27 +512,17 @@ static bool pp_takes(const mvp_gemm_args* a) {
   return t >= 200 && (t * 5 >= rounds * 256 * 4 || t >= 1024);
 }
 
-// mvp_gemm_bias_act_res (KA = mvp_gemm_args) and mvp_gemm_scaled (KA = mvp_gemm_kscaled, which the caller restricted to plain linear
-// GEMMs without split-K / stream-K): one validation and one tile rule for both.
-template <class KA>
-static int gemm_dispatch(const KA* a, void* stream) {
-  constexpr bool SC = has_col_scale<KA>::value;
-  if (!a || !a->a_hi || !a->w_hi) return MVP_EINVAL;
-  if constexpr (!SC) {
-    if (a->splitk == MVP_GEMM_STREAMK) return a->out_f16_col0 ? MVP_EINVAL : mvp_gemm_streamk(a, stream);
-  }
+// The whole kernel choice of mvp_gemm_bias_act_res and mvp_gemm_scaled (whose caller refused convolutions, split-K and the EXT epilogue
+// features first): every validation, then the instantiation.  Host only: no function attribute is set, nothing is launched.
+static int gemm_route(const mvp_gemm_args* a, Route* o) {
+  if (!a || !a->a_hi || !a->w_hi || a->splitk < 0) return MVP_EINVAL;
   if (a->pair_layout < 0 || a->pair_layout > MVP_PAIR_ILV32) return MVP_EINVAL;
   if (a->out_pair_layout != MVP_PAIR_SEPARATE &&
       (a->out_pair_layout != MVP_PAIR_A_ILV32 || !a->out_hi || (a->N & 31) || (a->precision != MVP_PREC_BF16X3 && a->precision != MVP_PREC_F16X2))) return MVP_EINVAL;
   if (a->out_f16_col0 != 0 && ((a->out_f16_col0 != -1 && ((a->out_f16_col0 < 0 ? -a->out_f16_col0 : a->out_f16_col0) & (a->out_f16_col0 < 0 ? 127 : 63))) || (a->precision != MVP_PREC_BF16X3 && a->precision != MVP_PREC_F16X2) || !a->out_hi ||
                                (!a->out_lo && a->out_pair_layout == MVP_PAIR_SEPARATE) || a->splitk > 1))
     return MVP_EINVAL;
-  if (a->M > 0 && a->N > 0 && (a->out_f32 || a->out_hi) && pp_takes(a)) {
-    if constexpr (SC)
-      return mvp_gemm_pp_scaled(a, stream);
-    else
-      return mvp_gemm_pp(a, stream);
-  }
+  if (a->M > 0 && a->N > 0 && (a->out_f32 || a->out_hi) && pp_takes(a)) return route_pp(a, o);
   if (a->pair_layout != MVP_PAIR_SEPARATE) return MVP_EINVAL;  // the tile kernels read separate hi / lo arrays
   if (a->M <= 0 || a->N <= 0 || a->K <= 0 || (a->K & (a->conv ? 31 : 63))) {
     // the one non-conv exception: K % 32 == 0 through the BK = 32 two-stage tile (ResNet stem: K = 147 padded to 160)
@@ -518,15 +535,12 @@ static int gemm_dispatch(const KA* a, void* stream) {
     // the two-product mode (opt-in): plain linear GEMMs of the ViT blocks, K % 64 == 0; a reduced tile rule (three shapes)
     if (a->conv || a->splitk > 1 || (a->K & 63) || a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi) return MVP_EINVAL;
     if (!a->out_f32 && !a->out_hi) return MVP_EINVAL;
-    hipStream_t s2 = (hipStream_t)stream;
-    if (a->N >= 1024) return launch_gemm<128, 128, 64, 2, 1, false, 8>(a, s2);
+    if (a->N >= 1024) return route_tile<128, 128, 64, 2, 1, false, 8>(o);
     const long t64 = (long)((a->M + 63) / 64) * ((a->N + 63) / 64);
-    return t64 <= 1280 ? launch_gemm<64, 64, 64, 2, 1>(a, s2) : launch_gemm<128, 64, 64, 2, 1>(a, s2);
+    return t64 <= 1280 ? route_tile<64, 64, 64, 2, 1>(o) : route_tile<128, 64, 64, 2, 1>(o);
   }
   if (!a->out_f32 && !a->out_hi) return MVP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
   const bool x3 = a->precision == MVP_PREC_BF16X3;
-  if constexpr (!SC) {
   if (a->conv) {
     if (!a->zero_page || a->cC <= 0 || (a->cC & 31) || a->ckh <= 0 || a->ckw <= 0 || a->cstride <= 0) return MVP_EINVAL;
     if (a->K != a->ckh * a->ckw * a->cC || a->cHo <= 0 || a->cWo <= 0 || (a->M % (a->cHo * a->cWo))) return MVP_EINVAL;
@@ -536,29 +550,27 @@ static int gemm_dispatch(const KA* a, void* stream) {
     // A K-tile must stay inside one tap: BK = 64 (whole-line rows, single stage: see the tile notes below) when
     // C % 64 == 0, else BK = 32 (any C % 32 == 0), two stages.
     if (x3 && (a->cC & 63) == 0) {
-      if (a->N <= 64) return launch_gemm<128, 64, 64, 3, 1, true>(a, s);
+      if (a->N <= 64) return route_tile<128, 64, 64, 3, 1, true>(o);
       // few-tile, long-K convolutions (ResNet layer3 / layer4 3x3 at 30^2 / 15^2: 226 / 116 tiles of 128x128):
       // smaller tiles so that every CU holds several workgroups of the single-stage loop
       const long c128 = (long)((a->M + 127) / 128) * ((a->N + 127) / 128);
       // (tile_policy is not consulted here: 128x128 for every convolution with >= 50 such tiles while ResNet forwards share the chip
       // measured 4638 img/s against 4565 with this rule — not worth a second rule)
-      if (c128 >= 300) return launch_gemm<128, 128, 64, 3, 1, true, 8>(a, s);
-      if (c128 >= 160) return launch_gemm<64, 128, 64, 3, 1, true>(a, s);
-      return launch_gemm<64, 64, 64, 3, 1, true>(a, s);
+      if (c128 >= 300) return route_tile<128, 128, 64, 3, 1, true, 8>(o);
+      if (c128 >= 160) return route_tile<64, 128, 64, 3, 1, true>(o);
+      return route_tile<64, 64, 64, 3, 1, true>(o);
     }
-    if (a->N > 64) return x3 ? launch_gemm<128, 128, 32, 3, 2, true>(a, s) : launch_gemm<128, 128, 32, 1, 2, true>(a, s);
-    return x3 ? launch_gemm<128, 64, 32, 3, 2, true>(a, s) : launch_gemm<128, 64, 32, 1, 2, true>(a, s);
+    if (a->N > 64) return x3 ? route_tile<128, 128, 32, 3, 2, true>(o) : route_tile<128, 128, 32, 1, 2, true>(o);
+    return x3 ? route_tile<128, 64, 32, 3, 2, true>(o) : route_tile<128, 64, 32, 1, 2, true>(o);
   }
-  }
-  if (a->K & 63) return launch_gemm<128, 64, 32, 3, 2>(a, s);
-  if constexpr (!SC) {
+  if (a->K & 63) return route_tile<128, 64, 32, 3, 2>(o);
   const bool ext = a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi;
   if (a->splitk > 1 && !ext) {  // (with the ReLU-gate / second-residual epilogues the request is ignored)
     if (a->splitk > 64 || a->K / 64 < a->splitk) return MVP_EINVAL;
-    if (splitk_wide(a->N)) return x3 ? launch_gemm_splitk<128, 128, 64, 3, 1>(a, s) : launch_gemm_splitk<128, 128, 64, 1, 2>(a, s);
-    return x3 ? launch_gemm_splitk<128, 64, 64, 3, 1>(a, s) : launch_gemm_splitk<128, 64, 64, 1, 2>(a, s);
+    if (splitk_wide(a->N)) return x3 ? route_splitk<128, 128, 64, 3, 1>(o) : route_splitk<128, 128, 64, 1, 2>(o);
+    return x3 ? route_splitk<128, 64, 64, 3, 1>(o) : route_splitk<128, 64, 64, 1, 2>(o);
   }
-  }
+  // Diagnostic override (tools/gemm_bench.py): -DMVP_F_BM=.. -DMVP_F_BN=.. -DMVP_F_BK=.. -DMVP_F_ST=..
 #ifdef MVP_F_BM
 #ifndef MVP_F_NW
 #define MVP_F_NW 4
@@ -566,8 +578,8 @@ static int gemm_dispatch(const KA* a, void* stream) {
 #ifndef MVP_F_WNW
 #define MVP_F_WNW 2
 #endif
-  return x3 ? launch_gemm<MVP_F_BM, MVP_F_BN, MVP_F_BK, 3, MVP_F_ST, false, MVP_F_NW, MVP_F_WNW>(a, s)
-            : launch_gemm<MVP_F_BM, MVP_F_BN, MVP_F_BK, 1, MVP_F_ST, false, MVP_F_NW, MVP_F_WNW>(a, s);
+  return x3 ? route_tile<MVP_F_BM, MVP_F_BN, MVP_F_BK, 3, MVP_F_ST, false, MVP_F_NW, MVP_F_WNW>(o)
+            : route_tile<MVP_F_BM, MVP_F_BN, MVP_F_BK, 1, MVP_F_ST, false, MVP_F_NW, MVP_F_WNW>(o);
 #else
   // Tile choice, split mode (measured on MI355X, tools/gemm_bench.py --tiles at M = 3152 and M = 12608; us, old -> new):
   //   qkv 41.3 -> 37.2 / 150.8 -> 138.6, proj 21.1 -> 17.2 / 63.7 -> 49.5, fc1 62.7 -> 51.3 / 193.8 -> 180.6,
@@ -586,43 +598,58 @@ static int gemm_dispatch(const KA* a, void* stream) {
   static const int big_env = [] { const char* e = getenv("MVP_GEMM_BIG"); return e ? atoi(e) : -1; }();
   const int big = big_env >= 0 ? big_env : ((a->tile_policy & MVP_TILES_SHARED) ? 1 : 0);
   if (x3 && big && !(a->N <= 256 && a->K >= 2048)) {
-    if (a->N >= 1024 || big == 1) return launch_gemm<128, 128, 64, 3, 1, false, 8>(a, s);
-    return launch_gemm<128, 64, 64, 3, 1>(a, s);
+    if (a->N >= 1024 || big == 1) return route_tile<128, 128, 64, 3, 1, false, 8>(o);
+    return route_tile<128, 64, 64, 3, 1>(o);
   }
   if (x3) {
     if (a->N <= 256 && a->K >= 2048) {  // probe head: few tiles, long K
-      if (a->M >= 8192) return launch_gemm<128, 64, 64, 3, 1>(a, s);
-      return launch_gemm<64, 64, 64, 3, 2>(a, s);
+      if (a->M >= 8192) return route_tile<128, 64, 64, 3, 1>(o);
+      return route_tile<64, 64, 64, 3, 2>(o);
     }
     if (a->N >= 1024) {
       // one round of 128x128 tiles (2 resident per CU = 512 slots) or many rounds: big tiles; in between the
       // second, mostly empty round costs more than the smaller tile's extra operand traffic
       // 8 waves (4x2) on the 128x128 tile: same LDS / residency, 4 waves per SIMD hide the load phase better
       // (M = 12608: qkv 136.0 -> 128.4 us, fc1 168.2 -> 164.5; M = 3152: 39.0 -> 38.4)
-      if (t128 <= 512 || t128 >= 1536) return launch_gemm<128, 128, 64, 3, 1, false, 8>(a, s);
-      return launch_gemm<64, 128, 64, 3, 1>(a, s);
+      if (t128 <= 512 || t128 >= 1536) return route_tile<128, 128, 64, 3, 1, false, 8>(o);
+      return route_tile<64, 128, 64, 3, 1>(o);
     }
     // long-K, mid-N GEMMs with many tiles (the DPT probe's coarse-grid input gradients: M = 12544, N = 512, K = 4608): the tile the
     // convolutions of the same shape use (165 us against 244 on 128x64)
-    if (a->K >= 4096 && t128 >= 300) return launch_gemm<128, 128, 64, 3, 1, false, 8>(a, s);
+    if (a->K >= 4096 && t128 >= 300) return route_tile<128, 128, 64, 3, 1, false, 8>(o);
     const long t64 = (long)((a->M + 63) / 64) * ((a->N + 63) / 64);
-    if (t64 <= 1280) return launch_gemm<64, 64, 64, 3, 1>(a, s);  // 5 resident per CU
-    return launch_gemm<128, 64, 64, 3, 1>(a, s);
+    if (t64 <= 1280) return route_tile<64, 64, 64, 3, 1>(o);  // 5 resident per CU
+    return route_tile<128, 64, 64, 3, 1>(o);
   }
-  if (t128 >= 400) return launch_gemm<128, 128, 64, 1, 2>(a, s);
-  return launch_gemm<64, 64, 64, 1, 2>(a, s);
+  if (t128 >= 400) return route_tile<128, 128, 64, 1, 2>(o);
+  return route_tile<64, 64, 64, 1, 2>(o);
 #endif
 }
 
-extern "C" int mvp_gemm_bias_act_res(const mvp_gemm_args* a, void* stream) { return gemm_dispatch(a, stream); }
+
+extern "C" int mvp_gemm_route(const mvp_gemm_args* a, mvp_gemm_route_t* out) {
+  Route r;
+  const int e = out ? gemm_route(a, &r) : MVP_EINVAL;
+  if (e == MVP_OK) *out = r.r;
+  return e;
+}
+
+extern "C" int mvp_gemm_bias_act_res(const mvp_gemm_args* a, void* stream) {
+  Route r;
+  const int e = gemm_route(a, &r);
+  return e != MVP_OK ? e : r.launch(a, (hipStream_t)stream);
+}
 
 extern "C" int mvp_gemm_scaled(const mvp_gemm_scaled_args* a, void* stream) {
   if (!a || !a->col_scale || ((size_t)a->col_scale & 15)) return MVP_EINVAL;
   const mvp_gemm_args& g = a->gemm;
-  // plain linear GEMMs: no convolution, split-K / stream-K or EXT epilogue features (masks, pair residuals, residual2, act_after_res)
+  // plain linear GEMMs: no convolution, split-K or EXT epilogue features (masks, pair residuals, residual2, act_after_res)
   if (g.conv || (g.splitk != 0 && g.splitk != 1) || g.relu_mask || g.out_mask || g.residual2 || g.act_after_res || g.residual_hi) return MVP_EINVAL;
+  Route r;
+  const int e = gemm_route(&g, &r);
+  if (e != MVP_OK) return e;
   mvp_gemm_kscaled k;
   static_cast<mvp_gemm_args&>(k) = g;
   k.col_scale = a->col_scale;
-  return gemm_dispatch(&k, stream);
+  return r.launch_scaled(&k, (hipStream_t)stream);
 }

@@ -39,6 +39,8 @@ struct mvp_gemm_kscaled : mvp_gemm_args {
 };
 // gemm_pp.hip's entry for these arguments (mvp_gemm_scaled in gemm.hip dispatches to it by the same rule as mvp_gemm_bias_act_res)
 __attribute__((visibility("hidden"))) int mvp_gemm_pp_scaled(const mvp_gemm_kscaled* a, void* stream);
+// mvp_gemm_pp's argument checks (gemm.hip routes a GEMM to that kernel only when they pass)
+__attribute__((visibility("hidden"))) int pp_check(const mvp_gemm_args* a);
 
 namespace {
 template <class T, class = void>

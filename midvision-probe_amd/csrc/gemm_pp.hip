@@ -588,13 +588,15 @@ int launch_pp_scaled(const mvp_gemm_kscaled* a, hipStream_t s) {
   return MVP_OK;
 }
 
-// The argument checks of mvp_gemm_pp (both entries)
+}  // namespace
+
+// The argument checks of mvp_gemm_pp (both entries, and gemm.hip's route to this kernel)
 int pp_check(const mvp_gemm_args* a) {
   if (!a || !a->a_hi || !a->w_hi) return MVP_EINVAL;
   if (a->pair_layout < 0 || a->pair_layout > (MVP_PAIR_A_ILV32 | MVP_PAIR_W_ILV32)) return MVP_EINVAL;
   const bool ilva = a->pair_layout & MVP_PAIR_A_ILV32, ilvw = a->pair_layout & MVP_PAIR_W_ILV32;
   if ((!ilva && !a->a_lo) || (!ilvw && !a->w_lo)) return MVP_EINVAL;
-  if (a->M <= 0 || a->N <= 0 || a->K < 64 || (a->K & 31) || a->splitk > 1) return MVP_EINVAL;
+  if (a->M <= 0 || a->N <= 0 || a->K < 64 || (a->K & 31) || a->splitk > 1 || a->splitk < 0) return MVP_EINVAL;
   if (a->conv) {  // gemm.hip's conv contract (mvp_gemm_bias_act_res validates the same)
     if (ilva || a->cC <= 0 || (a->cC & 31) || a->ckh <= 0 || a->ckw <= 0 || a->cstride <= 0 || a->cpad < 0 || a->cup < 0) return MVP_EINVAL;
     if (a->K != a->ckh * a->ckw * a->cC || a->cHo <= 0 || a->cWo <= 0 || (a->M % (a->cHo * a->cWo))) return MVP_EINVAL;
@@ -611,8 +613,6 @@ int pp_check(const mvp_gemm_args* a) {
   if ((int64_t)256 * a->lda * 2 >= 0x7fffff00ll || (int64_t)256 * a->ldw * 2 >= 0x7fffff00ll) return MVP_EINVAL;
   return MVP_OK;
 }
-
-}  // namespace
 
 extern "C" int mvp_gemm_pp(const mvp_gemm_args* a, void* stream) {
   if (pp_check(a) != MVP_OK) return MVP_EINVAL;

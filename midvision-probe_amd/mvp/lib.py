@@ -24,6 +24,7 @@ RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1, 2
 PAIR_SEPARATE, PAIR_A_ILV32, PAIR_W_ILV32 = 0, 1, 2  # mvp_gemm_args.pair_layout (bit flags)
 BN_RUNNING_MAX = 8  # MVP_BN_RUNNING_MAX: modules per mvp_bn_running_update_n launch
 TILES_SHARED, TILES_NO_PP, TILES_NO_UNI = 1, 2, 4
+ROUTE_PP, ROUTE_TILE, ROUTE_SPLITK, ROUTE_CONV = 1, 2, 3, 4  # mvp_gemm_route_t.family
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -76,6 +77,10 @@ class ClsRowsArgs(C.Structure):
 
 class GemmScaledArgs(C.Structure):  # mvp_gemm_scaled_args: LayerScale in the GEMM epilogue (ABI 7 addition)
     _fields_ = [("gemm", GemmArgs), ("col_scale", _vp)]
+
+
+class GemmRoute(C.Structure):  # mvp_gemm_route_t: the kernel mvp_gemm_bias_act_res runs (ABI 8)
+    _fields_ = [("family", _i), ("bm", _i), ("bn", _i), ("bk", _i), ("split", _i), ("nstage", _i), ("nw", _i), ("wnw", _i)]
 
 
 class PatchGatherLdArgs(C.Structure):  # mvp_patch_gather_ld_args: padded patch rows (ABI 7 addition)
@@ -223,8 +228,7 @@ SYMBOLS = {
     "mvp_patch_gather": PatchGatherArgs,
     "mvp_gemm_bias_act_res": GemmArgs,
     "mvp_gemm_splitk_workspace_bytes": None,
-    "mvp_gemm_streamk_workspace_bytes": None,
-    "mvp_gemm_streamk": GemmArgs,
+    "mvp_gemm_route": None,
     "mvp_layernorm_fwd": LayerNormArgs,
     "mvp_attention_fwd": AttentionArgs,
     "mvp_cls_rows": ClsRowsArgs,
@@ -311,8 +315,8 @@ def load() -> C.CDLL:
     lib.mvp_metrics_breakdown_workspace_bytes.restype = _i64
     lib.mvp_metrics_workspace_bytes.argtypes = [_i]
     lib.mvp_metrics_workspace_bytes.restype = _i64
-    lib.mvp_gemm_streamk_workspace_bytes.argtypes = []
-    lib.mvp_gemm_streamk_workspace_bytes.restype = _i64
+    lib.mvp_gemm_route.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmRoute)]
+    lib.mvp_gemm_route.restype = _i
     lib.mvp_gemm_splitk_workspace_bytes.argtypes = [_i, _i, _i]
     lib.mvp_gemm_splitk_workspace_bytes.restype = _i64
     lib.mvp_gemm_tn_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]

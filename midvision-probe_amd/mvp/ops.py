@@ -6,7 +6,8 @@ allocated by the caller (or by these helpers with torch.empty — plumbing only)
 """
 from __future__ import annotations
 
-import os
+import ctypes
+import functools
 from typing import Optional, Tuple
 
 import torch
@@ -56,34 +57,29 @@ def _traced(kind: str, tile: str, precision: int, work: float, fn) -> None:
     _TRACE.append((kind, tile, precision, work, e0, e1))
 
 
+@functools.lru_cache(maxsize=None)
+def _route_label(M: int, N: int, K: int, precision: int, splitk: int, tile_policy: int, a_ilv: bool = False, ext: bool = False) -> str:
+    """The kernel mvp_gemm_bias_act_res runs for a linear GEMM of this form (mvp_gemm_route: the library's rule, csrc/gemm.hip), "" where
+    it would refuse the arguments.  ``a_ilv``: interleaved A operand; ``ext``: an EXT epilogue (an output mask stands for all of them).
+    Operands are stand-ins: the query only tests pointers for NULL.  (Memoized: the library reads its overrides once per process.)"""
+    a = lib.GemmArgs(a_hi=16, a_lo=16, w_hi=16, w_lo=16, out_f32=16, out_hi=16, out_lo=16, M=M, N=N, K=K, lda=2 * K if a_ilv else K, ldw=K,
+                     ldr=N, ldo=N, ldob=N, precision=precision, splitk=splitk, tile_policy=tile_policy,
+                     pair_layout=lib.PAIR_A_ILV32 if a_ilv else lib.PAIR_SEPARATE, out_mask=16 if ext else None, ldm=N)
+    r = lib.GemmRoute()
+    if lib.load().mvp_gemm_route(ctypes.byref(a), ctypes.byref(r)) != 0:
+        return ""
+    if r.family == lib.ROUTE_PP:
+        return f"pp {r.bm}, {r.bn}, {r.bk}, {r.split}"
+    return f"{r.bm}, {r.bn}, {r.bk}, {r.split}, {r.nstage}" + (", splitk" if r.family == lib.ROUTE_SPLITK else "")
+
+
 def gemm_tile(M: int, N: int, K: int = 0, precision: int = PREC_BF16X3, splitk: int = 1, tile_policy: int = 0) -> str:
-    """Mirror of the tile choice in csrc/gemm.hip -> template arguments BM,BN,BK,SPLIT,NSTAGE."""
-    if splitk > 1:
-        bn = 128 if N >= 1024 else 64
-        return f"128, {bn}, 64, 3, 1, splitk" if precision == PREC_BF16X3 else f"128, {bn}, 64, 1, 2, splitk"
-    if precision in (PREC_BF16X3, lib.PREC_F16X2) and K % 32 == 0 and K >= 64 and not (N <= 256 and K >= 2048) and os.environ.get("MVP_GEMM_PP", "") != "0":
-        t256 = ((M + 255) // 256) * ((N + 255) // 256)  # pp_takes() of csrc/gemm.hip: the large-M ping-pong kernel
-        rounds = (t256 + 255) // 256
-        narrow = ((N + 255) // 256) * 256 * 7 > N * 8  # more than 1/8 of the tile grid's columns would be padding
-        if os.environ.get("MVP_GEMM_PP") == "1" or not narrow and (t256 >= 96 if tile_policy == 1 else (t256 >= 128 if K >= 2048 else t256 >= 200 and (t256 * 5 >= rounds * 1024 or t256 >= 1024))):
-            return f"pp 256, 256, 32, {2 if precision == lib.PREC_F16X2 else 3}"
-    t128 = ((M + 127) // 128) * ((N + 127) // 128)
-    if precision == lib.PREC_F16X2:  # the reduced rule of csrc/gemm.hip for the two-product mode
-        if N >= 1024:
-            return "128, 128, 64, 2, 1"
-        return "64, 64, 64, 2, 1" if ((M + 63) // 64) * ((N + 63) // 64) <= 1280 else "128, 64, 64, 2, 1"
-    if precision == PREC_BF16X3:
-        if N <= 256 and K >= 2048:
-            return "128, 64, 64, 3, 1" if M >= 8192 else "64, 64, 64, 3, 2"
-        if tile_policy == 1:  # MVP_TILES_SHARED
-            return "128, 128, 64, 3, 1"
-        if N >= 1024:
-            return "128, 128, 64, 3, 1" if (t128 <= 512 or t128 >= 1536) else "64, 128, 64, 3, 1"
-        if K >= 4096 and t128 >= 300:
-            return "128, 128, 64, 3, 1"
-        t64 = ((M + 63) // 64) * ((N + 63) // 64)
-        return "64, 64, 64, 3, 1" if t64 <= 1280 else "128, 64, 64, 3, 1"
-    return "128, 128, 64, 1, 2" if t128 >= 400 else "64, 64, 64, 1, 2"
+    """The kernel of a plain linear GEMM: "pp 256, 256, 32, SPLIT" (the large-M kernel) or the tile kernel's template arguments
+    "BM, BN, BK, SPLIT, NSTAGE" (+ ", splitk")."""
+    label = _route_label(M, N, K, precision, splitk, tile_policy)
+    if not label:
+        raise lib.MvpError(f"mvp_gemm_route: no kernel takes M={M} N={N} K={K} precision={precision} splitk={splitk}")
+    return label
 
 
 def _chk(t: torch.Tensor, dtype, name: str):
@@ -186,35 +182,14 @@ def splitk_auto(M: int, N: int, K: int) -> int:
     return 1
 
 
-_STREAMK_WS = {}  # (device, stream) -> zero-initialised stream-K workspace (tile counters reset themselves)
-_STREAMK_MODE = os.environ.get("MVP_STREAMK", "auto")  # "auto" | "0" | "1" (diagnostic override)
-
-
-def streamk_auto(M: int, N: int, K: int, precision: int) -> bool:
-    """Stream-K scheduling (csrc/gemm_sk.hip: 128x128x64 tiles, one workgroup per CU, equal k-iterations per CU) is OPT-IN
-    (MVP_STREAMK=1 or streamk=True).  Measured on MI355X (tools/gemm_bench.py --sk, bf16x3, us: tile kernel -> stream-K best
-    variant): B=16 qkv 39.8 -> 54.5, proj 20.3 -> 30.7, fc1 50.7 -> 69.1, fc2 61.5 -> 79.5; B=64 qkv 131 -> 170, fc2 169 -> 261.
-    One lock-stepped 8-wave workgroup per CU issues its LDS-DMA pieces (each costs the issuing wave 75-185 cycles) from far fewer
-    waves than five independent 64x64 workgroups do, and the partial-tile hand-over adds ~15 us per launch."""
-    return _STREAMK_MODE == "1"
-
-
 def _ws_key(device):
     # launches on one stream are ordered, so they may share a workspace; launches on different streams (mvp/pipeline.py) may not.
     # A pipelined forward is keyed by its SLOT, not by the stream it happens to be enqueued on: every slot's hipGraph is captured on
-    # one stream and replayed on whichever stream its turn falls on, so a stream-keyed workspace would be baked into several graphs
+    # one stream and replayed on whichever stream its turn falls on, so a workspace keyed by stream would be baked into several graphs
     # that replay side by side (ADVICE r2)
     if pipeline.pipelined():
         return (device, "slot", pipeline.current_slot())
     return (device, lib.stream_ptr())
-
-
-def _streamk_workspace(device) -> torch.Tensor:
-    key = _ws_key(device)
-    ws = _STREAMK_WS.get(key)
-    if ws is None:
-        ws = _STREAMK_WS[key] = torch.zeros(int(lib.load().mvp_gemm_streamk_workspace_bytes()), dtype=torch.uint8, device=device)
-    return ws
 
 
 def _splitk_workspace(M: int, N: int, S: int, device) -> torch.Tensor:
@@ -229,17 +204,16 @@ def _splitk_workspace(M: int, N: int, S: int, device) -> torch.Tensor:
 def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, out_f32=None, out: Optional[Pair] = None,
          act: int = lib.ACT_NONE, precision: int = PREC_BF16X3, lda=None, ldw=None, ldr=None, ldo=None, ldob=None,
          row_group=0, row_group_stride=0, row_group_off=0, res_row_mod=0, act_after_res=False, out_mask=None, ldm=0,
-         splitk: Optional[int] = None, residual_pair: Optional[Pair] = None, streamk: Optional[bool] = None,
+         splitk: Optional[int] = None, residual_pair: Optional[Pair] = None,
          w_ilv: Optional[torch.Tensor] = None, f16_col0: int = 0, col_scale: Optional[torch.Tensor] = None) -> None:
     """Y = act(A Wᵀ + bias) + residual (see mvp_gemm_bias_act_res).
-    col_scale: fp32 [N] LayerScale vector: Y = col_scale * act(A Wᵀ + bias) + residual in the epilogue (mvp_gemm_scaled; never split-K or
-    stream-K, which do not take a scale).  splitk: None = automatic, 1 = off.
+    col_scale: fp32 [N] LayerScale vector: Y = col_scale * act(A Wᵀ + bias) + residual in the epilogue (mvp_gemm_scaled; never split-K,
+    which does not take a scale).  splitk: None = automatic, 1 = off.
     f16_col0 > 0: columns from there on of the pair output are written as hi = fp16, lo = bf16 (mvp_gemm_args.out_f16_col0: the V
     third of the fused qkv projection for ``attention(..., v_f16=True)``); f16_col0 = -1: EVERY column as the activation operand of a
-    PREC_F16X2 GEMM (``split_f16_comp``'s form: fc1 -> fc2); no split-K / stream-K either way.
+    PREC_F16X2 GEMM (``split_f16_comp``'s form: fc1 -> fc2); no split-K either way.
     residual_pair: the residual as a bf16 pair (hi, lo) instead of / in addition to the fp32 ``residual``.
-    streamk: None = automatic (streamk_auto), True / False force the stream-K kernel on / off.
-    w_ilv: the same weights as ``interleave_pair(w)``; handed to the large-M kernel when the dispatch rule picks it."""
+    w_ilv: the same weights as ``interleave_pair(w)``; handed over when the library routes the GEMM to the large-M kernel."""
     a_ilv, o_ilv = isinstance(a, IlvPair), isinstance(out, IlvPair)
     if a_ilv:
         a, lda = (a.t, None), (lda if lda is not None else 2 * K)
@@ -258,33 +232,27 @@ def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, 
     args.out_pair_layout = lib.PAIR_A_ILV32 if o_ilv else lib.PAIR_SEPARATE
     if f16_col0:
         args.out_f16_col0 = int(f16_col0)
-        splitk, streamk = 1, False
-    if precision == lib.PREC_F16X2:  # two products per contraction: plain linear GEMMs, no split-K / stream-K (mvp_hip.h)
-        splitk, streamk = 1, False
+        splitk = 1
+    if precision == lib.PREC_F16X2:  # two products per contraction: plain linear GEMMs, no split-K (mvp_hip.h)
+        splitk = 1
     if col_scale is not None:
         _chk(col_scale, torch.float32, "gemm.col_scale")
-        splitk, streamk = 1, False
+        splitk = 1
     if out_mask is not None:
         args.out_mask, args.ldm = lib.ptr(out_mask), ldm or N
     if residual_pair is not None:
         args.residual_hi, args.residual_lo = lib.ptr(residual_pair[0]), lib.ptr(residual_pair[1])
     S = 1
     plain = out_mask is None and not act_after_res and residual_pair is None
-    if (a_ilv or o_ilv) and (not plain or splitk not in (None, 1) or streamk):
-        raise lib.MvpError("interleaved pair operands: plain GEMMs only (no masks, split-K or stream-K)")
-    use_sk = plain and not (a_ilv or o_ilv) and splitk is None and (streamk_auto(M, N, K, precision) if streamk is None else bool(streamk))
-    if use_sk:
-        ws = _streamk_workspace(a[0].device)
-        args.splitk, args.splitk_ws, args.splitk_ws_bytes = -1, lib.ptr(ws), ws.numel()
-    elif plain and not a_ilv:
+    if (a_ilv or o_ilv) and (not plain or splitk not in (None, 1)):
+        raise lib.MvpError("interleaved pair operands: plain GEMMs only (no masks or split-K)")
+    if plain and not a_ilv:
         S = splitk_auto(M, N, K) if splitk is None else int(splitk)
     if S > 1:
         ws = _splitk_workspace(M, N, S, a[0].device)
         args.splitk, args.splitk_ws, args.splitk_ws_bytes = S, lib.ptr(ws), ws.numel()
-    tile = gemm_tile(M, N, K, precision, S, args.tile_policy) if (w_ilv is not None or _TRACE is not None) and not a_ilv else ""
-    if a_ilv:
-        tile = f"pp 256, 256, 32, {2 if precision == lib.PREC_F16X2 else 3}"
-    if w_ilv is not None and plain and not use_sk and S <= 1 and tile.startswith("pp ") and ldw is None:
+    tile = _route_label(M, N, K, precision, S, args.tile_policy, a_ilv, not plain) if (w_ilv is not None or _TRACE is not None) else ""
+    if w_ilv is not None and tile.startswith("pp ") and ldw is None:
         args.w_hi, args.w_lo, args.ldw = lib.ptr(w_ilv), None, 2 * K
         args.pair_layout |= lib.PAIR_W_ILV32
     if col_scale is not None:
@@ -298,7 +266,7 @@ def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, 
     e0.record()
     lib.call(name, args)
     e1.record()
-    _TRACE.append(("gemm", "streamk 128, 128, 64" if use_sk else tile, precision, 2.0 * M * N * K, e0, e1))
+    _TRACE.append(("gemm", tile, precision, 2.0 * M * N * K, e0, e1))
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: Pair, M: int, Cdim: int, eps: float,

@@ -230,8 +230,9 @@ class ViTEngine:
             # When every GEMM of a block goes to the large-M kernel (M fills whole rounds of 256x256 tiles: grouped forwards), its A
             # operands — LayerNorm output, attention output, fc1 output — are kept as hi|lo-interleaved arrays (ops.IlvPair): a 32-deep
             # k-step of a row is then one whole 128-byte line for the LDS-DMA (2-3 % per GEMM on top of the interleaved weights).
+            gp = lib.PREC_F16X2 if self.f16x2 else pr  # precision of the four block GEMMs
             ilv = (pr == PREC_BF16X3 and os.environ.get("MVP_ILV", "1") != "0" and C % 32 == 0 and self.hidden % 32 == 0 and
-                   all(ops.gemm_tile(M, n, k, pr, 1, pipeline.tile_policy()).startswith("pp ") for n, k in ((3 * C, C), (C, C), (self.hidden, C), (C, self.hidden))))
+                   all(ops.gemm_tile(M, n, k, gp, 1, pipeline.tile_policy()).startswith("pp ") for n, k in ((3 * C, C), (C, C), (self.hidden, C), (C, self.hidden))))
             xfull = torch.empty(M + headroom * N, C, dtype=torch.float32, device=dev)
             ws = dict(
                 xfull=xfull, headroom=headroom, x=xfull[headroom * N:],

@@ -25,11 +25,11 @@ def test_header_symbols_are_exported_and_bound():
         assert hasattr(so, name), name
 
 
-def test_info_and_strerror():
+def test_info_reports_abi_8_and_strerror():
     from mvp import lib
 
     inf = lib.info()
-    assert inf.abi_version == 7
+    assert inf.abi_version == 8
     assert lib.load().mvp_strerror(-1).decode().startswith("invalid argument")
 
 

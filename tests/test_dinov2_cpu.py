@@ -152,7 +152,8 @@ def test_new_exports_validate_arguments():
 
 
 def test_new_code_objects_have_no_private_segment():
-    """The LayerScale instantiations of the large-M kernel and of the tile kernels keep every value in registers (no scratch)."""
+    """Every kernel of the two GEMM objects — the large-M kernel and the tile kernels, their LayerScale instantiations among them —
+    keeps every value in registers (no scratch)."""
     import shutil
     import tempfile
 
@@ -160,7 +161,7 @@ def test_new_code_objects_have_no_private_segment():
     tool = lambda n: shutil.which(n) or os.path.join("/opt/rocm/llvm/bin", n)  # noqa: E731
     objs = [os.path.join(PKG, "csrc", "build", f) for f in ("gemm_pp.o", "gemm.o")]
     with tempfile.TemporaryDirectory() as td:
-        seen = 0
+        seen = scaled = 0
         for o in objs:  # the device code object: the object's offload bundle (.hip_fatbin), unbundled for gfx950
             fb, co = os.path.join(td, "fatbin"), os.path.join(td, os.path.basename(o) + ".co")
             subprocess.run([tool("llvm-objcopy"), f"--dump-section=.hip_fatbin={fb}", o, os.path.join(td, "host.o")], check=True)
@@ -170,12 +171,11 @@ def test_new_code_objects_have_no_private_segment():
             notes = subprocess.run([readelf, "--notes", co], check=True, capture_output=True, text=True).stdout
             for block in notes.split(".name:")[1:]:
                 name = block.split("\n", 1)[0].strip()
-                if "mvp_gemm_kscaled" not in name:
-                    continue
                 m = re.search(r"\.private_segment_fixed_size:\s+(\d+)", block)
                 assert m and int(m.group(1)) == 0, (name, m and m.group(1))
                 seen += 1
-        assert seen >= 8, seen
+                scaled += "mvp_gemm_kscaled" in name
+        assert seen >= 64 and scaled >= 8, (seen, scaled)
     assert os.path.exists(so)
 
 

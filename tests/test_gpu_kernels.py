@@ -141,56 +141,6 @@ def test_gemm_splitk(dev, precision):
         ops.gemm(ap, wp, M, N, K, out_f32=torch.empty(M, N, device=dev), precision=pr, splitk=16)
 
 
-@pytest.mark.parametrize("precision", ["bf16x3", "bf16"])
-def test_gemm_streamk(dev, precision):
-    """Stream-K kernel (gemm_sk.hip): parity with fp64 on the four backbone shapes + ragged / tiny ones (M, N not multiples of
-    128; fewer k-iterations than CUs; a single tile), every epilogue form the backbone uses, bit-reproducible across launches,
-    shapes alternating on ONE workspace (tile counters must return to zero), and agreement with the tile-per-workgroup kernel."""
-    from mvp import lib, ops
-    from mvp.vit import parse_precision
-
-    pr = parse_precision(precision)
-    tol = 2e-5 if pr == lib.PREC_BF16 else 5e-5
-    cases = []
-    for (M, N, K) in ((3152, 2304, 768), (3152, 768, 768), (3152, 3072, 768), (3152, 768, 3072), (3136, 256, 3072), (777, 1280, 1024),
-                      (130, 72, 768), (64, 128, 64), (19216, 768, 768)):
-        g = torch.Generator().manual_seed(M + N + K)
-        a, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05
-        bias, res = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
-        ap, wp = ops.split_bf16(a.to(dev), pr), ops.split_bf16(w.to(dev), pr)
-        if pr == lib.PREC_BF16:
-            a, w = _bf16_round(a), _bf16_round(w)
-        ref = F.gelu(a.double() @ w.double().t() + bias.double()) + res.double()
-        cases.append((M, N, K, ap, wp, bias.to(dev), res.to(dev), ref.numpy()))
-    outs = []
-    for rep in range(2):
-        for (M, N, K, ap, wp, bias, res, ref) in cases:
-            out = torch.full((M, N), float("nan"), device=dev)
-            op = ops.empty_pair((M, N), lib.PREC_BF16X3, dev)
-            ops.gemm(ap, wp, M, N, K, bias=bias, residual=res, out_f32=out, out=op, act=lib.ACT_GELU, precision=pr, streamk=True)
-            torch.cuda.synchronize()
-            assert rel_l2(out.cpu().numpy(), ref) < tol, (M, N, K)
-            assert rel_l2((op[0].float() + op[1].float()).cpu().numpy(), ref) < tol + 2e-5
-            outs.append(out)
-    n = len(cases)
-    for i in range(n):
-        assert torch.equal(outs[i], outs[n + i]), "stream-K result must be bit-reproducible"
-    # in-place residual stream (x += proj(..)), as the ViT blocks use it, vs the tile kernel
-    M, N, K, ap, wp, bias, res, ref = cases[1]
-    x1, x2 = res.clone(), res.clone()
-    ops.gemm(ap, wp, M, N, K, bias=bias, residual=x1, out_f32=x1, precision=pr, streamk=True)
-    ops.gemm(ap, wp, M, N, K, bias=bias, residual=x2, out_f32=x2, precision=pr, streamk=False, splitk=1)
-    assert rel_l2(x1.cpu().numpy(), x2.cpu().numpy()) < 1e-6
-    # features the stream-K kernel does not carry are refused, not silently dropped
-    with pytest.raises(lib.MvpError):
-        a = lib.GemmArgs(ap[0].data_ptr(), ap[1].data_ptr() if ap[1] is not None else None, wp[0].data_ptr(), wp[1].data_ptr() if wp[1] is not None else None,
-                         None, None, x1.data_ptr(), None, None, M, N, K, K, K, N, N, N, 0, pr, 0, 0, 0, 0)
-        a.splitk, a.act_after_res = -1, 1
-        ws = ops._streamk_workspace(dev)
-        a.splitk_ws, a.splitk_ws_bytes = ws.data_ptr(), ws.numel()
-        lib.call("mvp_gemm_bias_act_res", a)
-
-
 def test_gemm_row_remap(dev):
     """Patch-embed form: rows written behind a CLS slot, pos-embed residual indexed mod hw."""
     from mvp import lib, ops
@@ -757,7 +707,10 @@ def test_universal_epilogue_bits_equal_the_row_guarded_one(dev, shape):
 @pytest.mark.parametrize("shape", [(18912, 3072, 768), (5000, 768, 3072), (300, 512, 96)])
 def test_gemm_pp_interleaved_layouts_match_separate(dev, shape):
     """mvp_gemm_args.pair_layout / out_pair_layout: the large-M kernel on hi|lo-interleaved A and / or W operands, and writing an
-    interleaved output pair, returns exactly the bits it returns on separate arrays (ragged M and N included)."""
+    interleaved output pair, returns exactly the bits it returns on separate arrays (ragged M and N included).  mvp_gemm_pp is called
+    directly: at the two smaller shapes the dispatch rule picks the tile kernels for separate operands."""
+    import ctypes as C
+
     from mvp import lib, ops
 
     M, N, K = shape
@@ -766,24 +719,31 @@ def test_gemm_pp_interleaved_layouts_match_separate(dev, shape):
     ai.t.copy_(ops.interleave_pair(ap))
     wi = ops.interleave_pair(wp)
     assert torch.equal(ai.separate()[0], ap[0]) and torch.equal(ai.separate()[1], ap[1])
-    base = ops.empty_pair((M, N), lib.PREC_BF16X3, dev)
-    import os
+    assert ops.gemm_tile(M, N, K).startswith("pp ") == (shape == (18912, 3072, 768))
+    so = lib.load()
 
-    os.environ["MVP_GEMM_PP"] = "1"  # (the python-side mirror of the dispatch rule, read per call: hand the interleaved weights over)
-    try:
-        ops.gemm(ap, wp, M, N, K, bias=bias, out=base, act=lib.ACT_GELU, splitk=1)
-        for a_in, w_ilv, o_ilv in ((ai, None, False), (ap, wi, False), (ai, wi, False), (ai, wi, True), (ap, None, True)):
-            if o_ilv:
-                out = ops.IlvPair(M, N, dev)
-                out.t.fill_(float("nan"))
-            else:
-                out = ops.empty_pair((M, N), lib.PREC_BF16X3, dev)
-            ops.gemm(a_in, wp, M, N, K, bias=bias, out=out, act=lib.ACT_GELU, w_ilv=w_ilv)
-            torch.cuda.synchronize()
-            got = out.separate() if o_ilv else out
-            assert torch.equal(got[0], base[0]) and torch.equal(got[1], base[1]), (shape, type(a_in).__name__, w_ilv is not None, o_ilv)
-    finally:
-        del os.environ["MVP_GEMM_PP"]
+    def run(a_ilv, w_ilv, o_ilv):
+        out = ops.IlvPair(M, N, dev) if o_ilv else None
+        sep = None if o_ilv else ops.empty_pair((M, N), lib.PREC_BF16X3, dev)
+        if o_ilv:
+            out.t.fill_(float("nan"))
+        args = lib.GemmArgs(lib.ptr(ai.t if a_ilv else ap[0]), None if a_ilv else lib.ptr(ap[1]), lib.ptr(wi if w_ilv else wp[0]),
+                            None if w_ilv else lib.ptr(wp[1]), lib.ptr(bias), None, None, lib.ptr(out.t if o_ilv else sep[0]),
+                            None if o_ilv else lib.ptr(sep[1]), M, N, K, 2 * K if a_ilv else K, 2 * K if w_ilv else K, N, N,
+                            2 * N if o_ilv else N, lib.ACT_GELU, lib.PREC_BF16X3, 0, 0, 0, 0)
+        args.pair_layout = (lib.PAIR_A_ILV32 if a_ilv else 0) | (lib.PAIR_W_ILV32 if w_ilv else 0)
+        args.out_pair_layout = lib.PAIR_A_ILV32 if o_ilv else lib.PAIR_SEPARATE
+        if a_ilv or w_ilv:  # an interleaved operand: the dispatcher itself would send this call to the large-M kernel
+            r = lib.GemmRoute()
+            assert so.mvp_gemm_route(C.byref(args), C.byref(r)) == 0 and r.family == lib.ROUTE_PP, (shape, a_ilv, w_ilv, o_ilv)
+        lib.check(so.mvp_gemm_pp(C.byref(args), lib.stream_ptr()), "mvp_gemm_pp")
+        torch.cuda.synchronize()
+        return out.separate() if o_ilv else sep
+
+    base = run(False, False, False)
+    for a_ilv, w_ilv, o_ilv in ((True, False, False), (False, True, False), (True, True, False), (True, True, True), (False, False, True)):
+        got = run(a_ilv, w_ilv, o_ilv)
+        assert torch.equal(got[0], base[0]) and torch.equal(got[1], base[1]), (shape, a_ilv, w_ilv, o_ilv)
     r = F.gelu(ref)
     assert ((base[0].double() + base[1].double() - r).norm() / r.norm()).item() < 7e-5
 
