@@ -52,6 +52,13 @@ extern "C" {
 #define MVP_ACT_NONE 0
 #define MVP_ACT_GELU 1 /* exact erf GELU (torch nn.GELU default)            */
 #define MVP_ACT_RELU 2
+/* (added within ABI 8; constants only.)  The two sigmoid-form GELUs, x / (1 + exp2(-k(x))), for plain linear GEMMs — mvp_gemm_bias_act_res,
+ * mvp_gemm_pp, mvp_gemm_scaled, mvp_gemm_route: every kernel family and both epilogue outputs (pair, the MVP_PREC_F16X2 activation pair of
+ * out_f16_col0 = -1 included, and fp32), the same bits from each.  Convolutions (conv), split-K (splitk > 1) and the mask / pair-residual /
+ * residual2 / act_after_res forms return MVP_EINVAL for them, as does any act value outside MVP_ACT_NONE ... MVP_ACT_GELU_TANH.  Max |error|
+ * against fp64 over [-12, 12]: see DESIGN.md. */
+#define MVP_ACT_QUICK_GELU 3 /* x sigmoid(1.702 x): OpenAI CLIP                                          */
+#define MVP_ACT_GELU_TANH 4  /* x/2 (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))): torch nn.GELU("tanh"), SigLIP */
 
 typedef uint16_t mvp_bf16;
 
@@ -245,8 +252,8 @@ int mvp_gemm_scaled(const mvp_gemm_scaled_args*, void* stream);
  * ---------------------------------------------------------------------------------- */
 typedef struct {
   const float* x; const float* gamma; const float* beta;
-  mvp_bf16* out_hi; mvp_bf16* out_lo; /* lo may be NULL */
-  float* out_f32;                     /* optional fp32 copy, or NULL */
+  mvp_bf16* out_hi; mvp_bf16* out_lo; /* lo may be NULL; out_hi may be NULL when out_f32 is set (no pair output); both NULL: MVP_EINVAL */
+  float* out_f32;                     /* optional fp32 copy, or NULL.  out_f32 == x is allowed (in place: a row is read whole before it is written) */
   int M, C;                           /* C % 8 == 0, C <= 2048 */
   float eps;
   int out_layout;                     /* MVP_PAIR_SEPARATE, or MVP_PAIR_A_ILV32 (1): out_hi is ONE [M][C / 32][hi 32 | lo 32] array (row stride

@@ -517,6 +517,10 @@ static bool pp_takes(const mvp_gemm_args* a) {
 static int gemm_route(const mvp_gemm_args* a, Route* o) {
   if (!a || !a->a_hi || !a->w_hi || a->splitk < 0) return MVP_EINVAL;
   if (a->pair_layout < 0 || a->pair_layout > MVP_PAIR_ILV32) return MVP_EINVAL;
+  if (a->act < MVP_ACT_NONE || a->act > MVP_ACT_GELU_TANH) return MVP_EINVAL;
+  // QuickGELU / tanh-GELU: plain linear GEMMs (pair and / or fp32 output, fp32 residual); not the convolution, split-K and mask forms
+  if ((a->act == MVP_ACT_QUICK_GELU || a->act == MVP_ACT_GELU_TANH) &&
+      (a->conv || a->splitk > 1 || a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi)) return MVP_EINVAL;
   if (a->out_pair_layout != MVP_PAIR_SEPARATE &&
       (a->out_pair_layout != MVP_PAIR_A_ILV32 || !a->out_hi || (a->N & 31) || (a->precision != MVP_PREC_BF16X3 && a->precision != MVP_PREC_F16X2))) return MVP_EINVAL;
   if (a->out_f16_col0 != 0 && ((a->out_f16_col0 != -1 && ((a->out_f16_col0 < 0 ? -a->out_f16_col0 : a->out_f16_col0) & (a->out_f16_col0 < 0 ? 127 : 63))) || (a->precision != MVP_PREC_BF16X3 && a->precision != MVP_PREC_F16X2) || !a->out_hi ||

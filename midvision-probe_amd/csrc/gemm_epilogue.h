@@ -37,6 +37,15 @@
 struct mvp_gemm_kscaled : mvp_gemm_args {
   const float* col_scale;
 };
+// The same two argument structs for MVP_ACT_QUICK_GELU / MVP_ACT_GELU_TANH on the large-M kernel: kernel-argument types of their own, so
+// that those activations get instantiations of their own and the instantiations serving every other GEMM keep the code they had (the
+// kernel is spill-free by a narrow margin).  The epilogues compile the two activations in when ACTX is set.
+struct mvp_gemm_kact : mvp_gemm_args {
+  static constexpr bool act_ext = true;
+};
+struct mvp_gemm_kscaled_act : mvp_gemm_kscaled {
+  static constexpr bool act_ext = true;
+};
 // gemm_pp.hip's entry for these arguments (mvp_gemm_scaled in gemm.hip dispatches to it by the same rule as mvp_gemm_bias_act_res)
 __attribute__((visibility("hidden"))) int mvp_gemm_pp_scaled(const mvp_gemm_kscaled* a, void* stream);
 // mvp_gemm_pp's argument checks (gemm.hip routes a GEMM to that kernel only when they pass)
@@ -47,6 +56,11 @@ template <class T, class = void>
 struct has_col_scale : std::false_type {};
 template <class T>
 struct has_col_scale<T, std::void_t<decltype(std::declval<T&>().col_scale)>> : std::true_type {};
+
+template <class T, class = void>
+struct has_act_ext : std::false_type {};
+template <class T>
+struct has_act_ext<T, std::void_t<decltype(std::declval<T&>().act_ext)>> : std::true_type {};
 
 // The LayerScale product, never contracted with the residual add that follows it: the epilogues differ in what the compiler could fuse
 // it with, and a batch must get the same bits whichever GEMM kernel its forward uses (see gelu_erf below).
@@ -75,6 +89,25 @@ __device__ __forceinline__ float gelu_erf(float x) {
   poly = t * poly;
   const float pe = poly * __builtin_amdgcn_exp2f(-(b * b));
   return __builtin_fmaf(-fabsf(x), pe, fmaxf(x, 0.f));
+}
+
+// The two sigmoid-form GELUs, x / (1 + exp2(-k(x))): one v_exp_f32 and one v_rcp_f32 like gelu_erf, without its polynomial.  Contraction off
+// and every multiply-add spelled out for gelu_erf's reason: the same bits from every epilogue of every GEMM kernel family.
+// exp2 overflows to +inf for x << 0 and the reciprocal is then 0: the result is -0, the limit.
+//   QuickGELU (OpenAI CLIP): x sigmoid(1.702 x), k = 1.702 log2(e) x.
+__device__ __forceinline__ float quick_gelu(float x) {
+#pragma clang fp contract(off)
+  const float e = __builtin_amdgcn_exp2f(x * -2.4554669595930156f);
+  return x * __builtin_amdgcn_rcpf(1.0f + e);
+}
+//   tanh-GELU (SigLIP; torch nn.GELU(approximate="tanh")): x/2 (1 + tanh(u)) = x sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3),
+//   k = 2 log2(e) sqrt(2/pi) (x + 0.044715 x^3).
+__device__ __forceinline__ float gelu_tanh(float x) {
+#pragma clang fp contract(off)
+  const float c = (x * x) * 0.044715f;
+  const float u = __builtin_fmaf(c, x, x);
+  const float e = __builtin_amdgcn_exp2f(u * -2.302208198144325f);
+  return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
 // Logical tile index -> (tm, tn), XCD-region-major.  xcd_remap() hands each XCD one contiguous slice of the logical
@@ -113,7 +146,8 @@ __device__ __forceinline__ void region_tile(int L, int TM, int TN, int M, int N,
 // "swapped": a lane's 4 registers are 4 consecutive output columns of row lane & 15).  smem = the kernel's dynamic LDS (>= NW * 32 *
 // (WN + 4) * 4 bytes), free for reuse.  (m0, n0) = the workgroup's tile origin, (wm0, wn0) = this wave's offset inside it.
 // ARGS: mvp_gemm_args, or the same struct read in place from the kernel-argument segment (address space 4; gemm_pp.hip's tile loop).
-template <int NT, int MT, int WN, bool EXT, class ARGS>
+// ACTX = false compiles MVP_ACT_QUICK_GELU / MVP_ACT_GELU_TANH out (the large-M kernel's instantiations that never receive them).
+template <int NT, int MT, int WN, bool EXT, bool ACTX = true, class ARGS>
 __device__ __forceinline__ void gemm_epilogue(const ARGS& p, f32x4_t (&acc)[NT][MT], char* smem, const int wave, const int lane,
                                               const int m0, const int n0, const int wm0, const int wn0) {
   f16_saturate_mode();  // (the pair outputs' fp16 forms saturate instead of overflowing: mvp_common.h)
@@ -186,6 +220,12 @@ __device__ __forceinline__ void gemm_epilogue(const ARGS& p, f32x4_t (&acc)[NT][
       } else if (p.act == MVP_ACT_RELU && !x_act_after) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      } else if (ACTX && p.act == MVP_ACT_QUICK_GELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
+      } else if (ACTX && p.act == MVP_ACT_GELU_TANH) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
       }
       if constexpr (SC) {  // LayerScale: after bias and activation, before the residual
 #pragma unroll
@@ -437,6 +477,12 @@ __device__ __forceinline__ void gemm_epilogue_wide(const ARGS& p, f32x4_t (&acc)
       if (ACT == MVP_ACT_GELU) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[it][e] = gelu_erf(v[it][e]);
+      } else if (ACT == MVP_ACT_QUICK_GELU) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = quick_gelu(v[it][e]);
+      } else if (ACT == MVP_ACT_GELU_TANH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = gelu_tanh(v[it][e]);
       }
       if constexpr (SC) {
 #pragma unroll
@@ -494,10 +540,10 @@ __device__ __forceinline__ void gemm_epilogue_wide(const ARGS& p, f32x4_t (&acc)
 // vmcnt(0) per row group —, the DPT probe's convolutions, the serial loop's qkv / fc1) and the EXT instantiations of the large-M kernel.
 // Not covered (gemm_epilogue() stays): residual2, N % 8 != 0, unaligned or >= 2 GiB arrays (gemm_epilogue_uni_ok()).
 // The results are gemm_epilogue()'s bit for bit (same operations in the same order per element).
-// EXT = false compiles the gate / mask / pair-residual / post-residual-ReLU parts out, as in gemm_epilogue().
-__host__ __device__ __forceinline__ bool gemm_epilogue_uni_ok(const mvp_gemm_args& p) {
+// EXT = false compiles the gate / mask / pair-residual / post-residual-ReLU parts out, ACTX = false the two sigmoid-form GELUs, as in gemm_epilogue().
+__host__ __device__ __forceinline__ bool gemm_epilogue_uni_ok(const mvp_gemm_args& p, const bool actx = true) {
   if ((p.N & 7) || p.residual2) return false;
-  if (p.act != MVP_ACT_NONE && p.act != MVP_ACT_GELU && p.act != MVP_ACT_RELU) return false;
+  if (p.act != MVP_ACT_NONE && p.act != MVP_ACT_GELU && p.act != MVP_ACT_RELU && !(actx && (p.act == MVP_ACT_QUICK_GELU || p.act == MVP_ACT_GELU_TANH))) return false;
   const int64_t lim = 0x7fffff00ll;
   const int64_t rows = p.row_group > 0 ? ((int64_t)(p.M - 1) / p.row_group) * p.row_group_stride + p.row_group_off + p.row_group : p.M;
   const int64_t rrows = p.res_row_mod > 0 ? (int64_t)p.res_row_mod : rows;
@@ -512,7 +558,7 @@ __host__ __device__ __forceinline__ bool gemm_epilogue_uni_ok(const mvp_gemm_arg
   return true;
 }
 
-template <int NT, int MT, int WN, bool EXT, class ARGS = mvp_gemm_args, class HOOK>
+template <int NT, int MT, int WN, bool EXT, bool ACTX = true, class ARGS = mvp_gemm_args, class HOOK>
 __device__ __forceinline__ void gemm_epilogue_uni(const ARGS& p, f32x4_t (&acc)[NT][MT], char* smem, const int wave, const int lane,
                                                   const int m0, const int n0, const int wm0, const int wn0, HOOK&& after_first_loads) {
   f16_saturate_mode();  // (the pair outputs' fp16 forms saturate instead of overflowing: mvp_common.h)
@@ -615,6 +661,12 @@ __device__ __forceinline__ void gemm_epilogue_uni(const ARGS& p, f32x4_t (&acc)[
       } else if (p.act == MVP_ACT_RELU && !act_after) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[it][e] = fmaxf(v[it][e], 0.f);
+      } else if (ACTX && p.act == MVP_ACT_QUICK_GELU) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = quick_gelu(v[it][e]);
+      } else if (ACTX && p.act == MVP_ACT_GELU_TANH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[it][e] = gelu_tanh(v[it][e]);
       }
       if constexpr (SC) {
 #pragma unroll
@@ -692,7 +744,8 @@ __device__ __forceinline__ void gemm_epilogue_uni(const ARGS& p, f32x4_t (&acc)[
 }
 
 // Which wide-epilogue instantiation serves these arguments (0 = none: the generic epilogue).
-__host__ __device__ __forceinline__ int gemm_epilogue_wide_variant(const mvp_gemm_args& p) {
+// (`act`: the activation to choose for — p.act, or what gemm_epilogue_wide_variant_act() substitutes)
+__host__ __device__ __forceinline__ int gemm_epilogue_wide_variant(const mvp_gemm_args& p, const int act) {
   {  // the wide epilogues address every array through a buffer resource with 32-bit byte offsets: all of them below 2 GiB
     const int64_t lim = 0x7fffff00ll;
     const int64_t rows = p.row_group > 0 ? ((int64_t)(p.M - 1) / p.row_group) * p.row_group_stride + p.row_group_off + p.row_group : p.M;
@@ -702,21 +755,29 @@ __host__ __device__ __forceinline__ int gemm_epilogue_wide_variant(const mvp_gem
     if (p.relu_mask && rows * p.ldm > lim) return 0;
     if ((int64_t)p.N * 4 > lim) return 0;
   }
-  if (p.relu_mask && p.mask_mode == 2 && !p.out_mask && !p.residual2 && !p.act_after_res && !p.residual_hi && !p.residual && p.act == MVP_ACT_NONE &&
+  if (p.relu_mask && p.mask_mode == 2 && !p.out_mask && !p.residual2 && !p.act_after_res && !p.residual_hi && !p.residual && act == MVP_ACT_NONE &&
       p.out_f32 && !p.out_hi && !(p.N & 7) && !(p.ldm & 7) && !((size_t)p.relu_mask & 7) && !(p.ldo & 3) && !((size_t)p.out_f32 & 15) &&
       !(p.bias && ((size_t)p.bias & 15)))
     return 6;  // gated input gradient, fp32 out
   if (p.relu_mask || p.out_mask || p.residual2 || p.act_after_res || p.residual_hi) return 0;
-  if ((p.N & 7) || (p.act != MVP_ACT_NONE && p.act != MVP_ACT_GELU)) return 0;
+  if ((p.N & 7) || (act != MVP_ACT_NONE && act != MVP_ACT_GELU)) return 0;
   if (p.residual && ((p.ldr & 3) || ((size_t)p.residual & 15))) return 0;
   if (p.out_f32 && ((p.ldo & 3) || ((size_t)p.out_f32 & 15))) return 0;
   if (p.out_hi && ((p.ldob & 7) || ((size_t)p.out_hi & 15) || (p.out_lo && ((size_t)p.out_lo & 15)))) return 0;
   if (p.bias && ((size_t)p.bias & 15)) return 0;
-  const bool pair = p.out_hi != nullptr, f32 = p.out_f32 != nullptr, res = p.residual != nullptr, gelu = p.act == MVP_ACT_GELU;
+  const bool pair = p.out_hi != nullptr, f32 = p.out_f32 != nullptr, res = p.residual != nullptr, gelu = act == MVP_ACT_GELU;
   if (pair && !f32 && !res) return gelu ? 2 : 1;   // qkv / fc1
   if (f32 && !pair && res && !gelu) return 3;      // proj / fc2 / patch embedding
   if (f32 && !pair && !res) return gelu ? 5 : 4;
   return 0;
+}
+__host__ __device__ __forceinline__ int gemm_epilogue_wide_variant(const mvp_gemm_args& p) { return gemm_epilogue_wide_variant(p, p.act); }
+// The same for the instantiations of mvp_gemm_kact / mvp_gemm_kscaled_act, which only receive the two sigmoid-form GELUs: the forms erf-GELU
+// has (pair output = fc1: 7 / 9, fp32 output: 8 / 10, QuickGELU / tanh-GELU), under the same conditions.
+__host__ __device__ __forceinline__ int gemm_epilogue_wide_variant_act(const mvp_gemm_args& p) {
+  if (p.act != MVP_ACT_QUICK_GELU && p.act != MVP_ACT_GELU_TANH) return 0;
+  const int g = gemm_epilogue_wide_variant(p, MVP_ACT_GELU), t = p.act == MVP_ACT_GELU_TANH ? 2 : 0;
+  return g == 2 ? 7 + t : g == 5 ? 8 + t : 0;
 }
 
 }  // namespace

@@ -100,7 +100,8 @@ constexpr int PP_SMEM = 2 * PP_BUF_B;    // two k-step buffers = 128 KiB
 // acc += a_lo . w_lo, then acc += a_hi . w_hi, both f16 MFMAs.  Same arrays, layouts, staging and fragment reads (the halves are
 // 16-bit either way); per 32-deep k-step lo product first, then hi, k ascending — the order the tile kernels use, so the two families
 // stay bit-identical in this mode too.
-// KA: mvp_gemm_args, or mvp_gemm_kscaled (LayerScale in the epilogue: mvp_gemm_scaled).
+// KA: mvp_gemm_args, or mvp_gemm_kscaled (LayerScale in the epilogue: mvp_gemm_scaled); mvp_gemm_kact / mvp_gemm_kscaled_act: the same two for
+// MVP_ACT_QUICK_GELU / MVP_ACT_GELU_TANH, which only these instantiations implement (their wide epilogues and nothing else's).
 template <bool ILVA, bool ILVW, bool EXT, bool CONV = false, bool F16X2 = false, class KA = mvp_gemm_args>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const KA p) {
   static_assert(!(CONV && ILVA), "the convolution reads separate hi / lo activation arrays");
@@ -380,9 +381,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const KA p) {
 #ifndef MVP_PP_WIDE_EPILOGUE
 #define MVP_PP_WIDE_EPILOGUE 1  // 0 (diagnostic builds): always the generic epilogue
 #endif
-  const int wide = (!EXT && MVP_PP_WIDE_EPILOGUE) ? gemm_epilogue_wide_variant(p) : 0;  // wave-uniform: kernel arguments only
+  constexpr bool ACTX = has_act_ext<KA>::value;  // the instantiations of the two sigmoid-form GELUs (never EXT: the host refuses that)
+  static_assert(!(ACTX && EXT), "QuickGELU / tanh-GELU: plain epilogues only");
+  const int wide = (!EXT && MVP_PP_WIDE_EPILOGUE) ? (ACTX ? gemm_epilogue_wide_variant_act(p) : gemm_epilogue_wide_variant(p)) : 0;  // wave-uniform: kernel arguments only
   // EXT instantiations (masks, pair residuals, post-residual ReLU): the universal branch-free epilogue where it serves the form
-  const bool uni = EXT && MVP_PP_WIDE_EPILOGUE && gemm_epilogue_uni_ok(p) && !(p.tile_policy & MVP_TILES_NO_UNI);
+  const bool uni = EXT && MVP_PP_WIDE_EPILOGUE && gemm_epilogue_uni_ok(p, false) && !(p.tile_policy & MVP_TILES_NO_UNI);
 
   // ---------------------------------------------------------------- first tile: the cold prologue — HA0(0), HB(0), HA1(0), then what "P2(-1)" would issue
   int bid = blockIdx.x;
@@ -457,7 +460,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const KA p) {
     asm volatile("" : "+s"(kp));
     kargs_t& pe = *kp;
 #endif
-    switch (wide) {
+    switch (ACTX ? 0 : wide) {
       case 1: gemm_epilogue_wide<NT, MT, WN, MVP_ACT_NONE, false, false, true>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch); break;
       case 2: gemm_epilogue_wide<NT, MT, WN, MVP_ACT_GELU, false, false, true>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch); break;
       case 3: gemm_epilogue_wide<NT, MT, WN, MVP_ACT_NONE, true, true, false>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch); break;
@@ -467,11 +470,17 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const KA p) {
       default:
         if constexpr (EXT) {
           if (uni) {
-            gemm_epilogue_uni<NT, MT, WN, true>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch);
+            gemm_epilogue_uni<NT, MT, WN, true, false>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch);
             break;
           }
         }
-        gemm_epilogue<NT, MT, WN, EXT>(pe, acc, smem, wave, lane_e, m0c, n0c, wm0, wn0);
+        if constexpr (ACTX) {  // fc1 of the CLIP / SigLIP blocks (pair output), and the fp32-output form
+          if (wide == 7) { gemm_epilogue_wide<NT, MT, WN, MVP_ACT_QUICK_GELU, false, false, true>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch); break; }
+          if (wide == 8) { gemm_epilogue_wide<NT, MT, WN, MVP_ACT_QUICK_GELU, false, true, false>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch); break; }
+          if (wide == 9) { gemm_epilogue_wide<NT, MT, WN, MVP_ACT_GELU_TANH, false, false, true>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch); break; }
+          if (wide == 10) { gemm_epilogue_wide<NT, MT, WN, MVP_ACT_GELU_TANH, false, true, false>(pe, acc, scratch, wave, lane_e, m0c, n0c, wm0, wn0, prefetch); break; }
+        }
+        gemm_epilogue<NT, MT, WN, EXT, ACTX>(pe, acc, smem, wave, lane_e, m0c, n0c, wm0, wn0);
         // The generic epilogue guards its rows with branches, and hipcc's wait-count pass must assume that a skipped row leaves that
         // row's bias / residual / mask loads pending: without a wait it can SEE here it would protect their destination registers with
         // an s_waitcnt vmcnt(0) inside the main loop — one drain of the LDS-DMA pipeline per k-step, for every epilogue variant.
@@ -578,14 +587,29 @@ int launch_pp(const mvp_gemm_args* a, hipStream_t s) {
 
 // LayerScale GEMMs: the plain (non-EXT) instantiation only — the wide epilogues where they serve, the generic one otherwise (the caller
 // refused every EXT feature)
-template <bool ILVA, bool ILVW>
-int launch_pp_scaled(const mvp_gemm_kscaled* a, hipStream_t s) {
-  static int configured = (int)hipFuncSetAttribute((const void*)gemm_pp_kernel<ILVA, ILVW, false, false, false, mvp_gemm_kscaled>,
+template <bool ILVA, bool ILVW, class KA = mvp_gemm_kscaled>
+int launch_pp_scaled(const KA* a, hipStream_t s) {
+  static int configured = (int)hipFuncSetAttribute((const void*)gemm_pp_kernel<ILVA, ILVW, false, false, false, KA>,
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, PP_SMEM);
   if (configured != 0) return MVP_ELAUNCH;
-  hipLaunchKernelGGL((gemm_pp_kernel<ILVA, ILVW, false, false, false, mvp_gemm_kscaled>), dim3(pp_grid(a)), dim3(512), PP_SMEM, s, *a);
+  hipLaunchKernelGGL((gemm_pp_kernel<ILVA, ILVW, false, false, false, KA>), dim3(pp_grid(a)), dim3(512), PP_SMEM, s, *a);
   MVP_LAUNCH_CHECK();
   return MVP_OK;
+}
+
+// MVP_ACT_QUICK_GELU / MVP_ACT_GELU_TANH (KA = mvp_gemm_kact / mvp_gemm_kscaled_act): the plain instantiation of their own kernel-argument type,
+// both precisions.  Convolutions and the EXT epilogue features do not take these activations.
+inline bool pp_act_ext(const mvp_gemm_args* a) { return a->act == MVP_ACT_QUICK_GELU || a->act == MVP_ACT_GELU_TANH; }
+template <class KA>
+int launch_pp_act(const KA* a, hipStream_t s) {
+  if (a->conv || a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi) return MVP_EINVAL;
+  const bool ilva = a->pair_layout & MVP_PAIR_A_ILV32, ilvw = a->pair_layout & MVP_PAIR_W_ILV32;
+  if (a->precision == MVP_PREC_F16X2) {
+    if (ilva) return ilvw ? launch_pp_f16x2<true, true>(a, s) : launch_pp_f16x2<true, false>(a, s);
+    return ilvw ? launch_pp_f16x2<false, true>(a, s) : launch_pp_f16x2<false, false>(a, s);
+  }
+  if (ilva) return ilvw ? launch_pp_scaled<true, true>(a, s) : launch_pp_scaled<true, false>(a, s);
+  return ilvw ? launch_pp_scaled<false, true>(a, s) : launch_pp_scaled<false, false>(a, s);
 }
 
 }  // namespace
@@ -607,6 +631,8 @@ int pp_check(const mvp_gemm_args* a) {
   const bool f16x2 = a->precision == MVP_PREC_F16X2;
   if (f16x2 && (a->conv || a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi)) return MVP_EINVAL;
   if (!a->out_f32 && !a->out_hi) return MVP_EINVAL;
+  if (a->act < MVP_ACT_NONE || a->act > MVP_ACT_GELU_TANH) return MVP_EINVAL;
+  if (pp_act_ext(a) && (a->conv || a->relu_mask || a->out_mask || a->residual2 || a->act_after_res || a->residual_hi)) return MVP_EINVAL;
   if (a->out_pair_layout != MVP_PAIR_SEPARATE && (a->out_pair_layout != MVP_PAIR_A_ILV32 || !a->out_hi || (a->N & 31))) return MVP_EINVAL;
   if (a->out_f16_col0 != 0 && ((a->out_f16_col0 != -1 && ((a->out_f16_col0 < 0 ? -a->out_f16_col0 : a->out_f16_col0) & (a->out_f16_col0 < 0 ? 127 : 63))) || !a->out_hi || (!a->out_lo && a->out_pair_layout == MVP_PAIR_SEPARATE))) return MVP_EINVAL;
   // 32-bit per-lane byte offsets: 256 tile rows of the widest supported row must stay below 2 GiB
@@ -619,6 +645,13 @@ extern "C" int mvp_gemm_pp(const mvp_gemm_args* a, void* stream) {
   const bool ilva = a->pair_layout & MVP_PAIR_A_ILV32, ilvw = a->pair_layout & MVP_PAIR_W_ILV32;
   const bool f16x2 = a->precision == MVP_PREC_F16X2;
   hipStream_t st = (hipStream_t)stream;
+#ifndef MVP_PP_ONE
+  if (pp_act_ext(a)) {
+    mvp_gemm_kact k;
+    static_cast<mvp_gemm_args&>(k) = *a;
+    return launch_pp_act(&k, st);
+  }
+#endif
 #ifdef MVP_PP_ONE  // diagnostic builds: only the interleaved-operand instantiation (fast compiles of experiments)
   return (ilva && ilvw && !a->conv && !f16x2) ? launch_pp<true, true>(a, st) : MVP_EINVAL;
 #else
@@ -640,6 +673,11 @@ int mvp_gemm_pp_scaled(const mvp_gemm_kscaled* a, void* stream) {
 #ifdef MVP_PP_ONE
   return MVP_EINVAL;
 #else
+  if (pp_act_ext(a)) {
+    mvp_gemm_kscaled_act k;
+    static_cast<mvp_gemm_kscaled&>(k) = *a;
+    return launch_pp_act(&k, st);
+  }
   if (a->precision == MVP_PREC_F16X2) {
     if (ilva) return ilvw ? launch_pp_f16x2<true, true>(a, st) : launch_pp_f16x2<true, false>(a, st);
     return ilvw ? launch_pp_f16x2<false, true>(a, st) : launch_pp_f16x2<false, false>(a, st);

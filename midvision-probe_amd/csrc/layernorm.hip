@@ -76,7 +76,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const mvp_layernorm_args
         if (p.out_f16) split2_f16_comp(y[2 * e], y[2 * e + 1], h[e], l[e]);
         else split2_bf16(y[2 * e], y[2 * e + 1], h[e], l[e]);
       }
-      if (p.out_layout == MVP_PAIR_A_ILV32) {  // one array, hi | lo interleaved per 32 columns (an 8-element chunk never straddles a block)
+      if (!p.out_hi) {
+        // fp32 output only, possibly in place over x (this wave read its whole row before this first store, and no other wave touches the row)
+      } else if (p.out_layout == MVP_PAIR_A_ILV32) {  // one array, hi | lo interleaved per 32 columns (an 8-element chunk never straddles a block)
         const size_t oi = (size_t)row * 2 * p.C + ilv32_col(c * 8);
         store_out((u32x4_t*)(p.out_hi + oi), u32x4_t{h[0], h[1], h[2], h[3]}, MVP_LN_NT);
         store_out((u32x4_t*)(p.out_hi + oi + 32), u32x4_t{l[0], l[1], l[2], l[3]}, MVP_LN_NT);
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const mvp_layernorm_args
 }  // namespace
 
 extern "C" int mvp_layernorm_fwd(const mvp_layernorm_args* a, void* stream) {
-  if (!a || !a->x || !a->gamma || !a->beta || !a->out_hi) return MVP_EINVAL;
+  if (!a || !a->x || !a->gamma || !a->beta || (!a->out_hi && !a->out_f32)) return MVP_EINVAL;
   if (a->M <= 0 || a->C <= 0 || (a->C & 7) || a->C > 64 * 8 * LN_MAXV) return MVP_EINVAL;
   if (a->out_layout != MVP_PAIR_SEPARATE && (a->out_layout != MVP_PAIR_A_ILV32 || (a->C & 31))) return MVP_EINVAL;
   hipLaunchKernelGGL(layernorm_kernel, dim3((a->M + 3) / 4), dim3(256), 0, (hipStream_t)stream, *a);

@@ -164,6 +164,196 @@ def hf_vitmae_to_fused(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
+# ---------------------------------------------------------------- CLIP / SigLIP (language-supervised ViTs): architectures, random init, key layouts
+CLIP_ARCH = {  # open_clip arch -> (embed_dim, depth, patch, image size); heads = embed_dim / 64, MLP ratio 4
+    "ViT-B-16": (768, 12, 16, 224),
+    "ViT-L-14": (1024, 24, 14, 224),
+    "ViT-L-14-336": (1024, 24, 14, 336),
+}
+SIGLIP_ARCH = {  # timm model name -> (embed_dim, depth, patch, image size)
+    "vit_base_patch16_siglip_224": (768, 12, 16, 224),
+    "vit_base_patch16_siglip_384": (768, 12, 16, 384),
+    "vit_large_patch16_siglip_256": (1024, 24, 16, 256),
+    "vit_large_patch16_siglip_384": (1024, 24, 16, 384),
+}
+
+
+def _random_blocks(sd, prefix, names, embed_dim, depth, g):
+    """Blocks with non-trivial LayerNorm affines and biases (as random_dinov2_state_dict), under the given key names."""
+    def tn(*shape):
+        t = torch.empty(*shape)
+        torch.nn.init.trunc_normal_(t, std=0.02, a=-2.0, b=2.0, generator=g)
+        return t
+
+    hid = 4 * embed_dim
+    for i in range(depth):
+        p = f"{prefix}{i}."
+        for n in (names["norm1"], names["norm2"]):
+            sd[p + n + ".weight"] = 1.0 + 0.1 * torch.randn(embed_dim, generator=g)
+            sd[p + n + ".bias"] = 0.02 * torch.randn(embed_dim, generator=g)
+        sd[p + names["qkv_w"]], sd[p + names["qkv_b"]] = tn(3 * embed_dim, embed_dim), tn(3 * embed_dim)
+        sd[p + names["proj"] + ".weight"], sd[p + names["proj"] + ".bias"] = tn(embed_dim, embed_dim), tn(embed_dim)
+        sd[p + names["fc1"] + ".weight"], sd[p + names["fc1"] + ".bias"] = tn(hid, embed_dim), tn(hid)
+        sd[p + names["fc2"] + ".weight"], sd[p + names["fc2"] + ".bias"] = tn(embed_dim, hid), tn(embed_dim)
+
+
+_OPENCLIP_BLOCK = dict(norm1="ln_1", norm2="ln_2", qkv_w="attn.in_proj_weight", qkv_b="attn.in_proj_bias", proj="attn.out_proj", fc1="mlp.c_fc", fc2="mlp.c_proj")
+_TIMM_BLOCK = dict(norm1="norm1", norm2="norm2", qkv_w="attn.qkv.weight", qkv_b="attn.qkv.bias", proj="attn.proj", fc1="mlp.fc1", fc2="mlp.fc2")
+
+
+def random_clip_state_dict(embed_dim=768, depth=12, patch=16, img=224, seed=0, in_chans=3, out_dim=512) -> Dict[str, torch.Tensor]:
+    """Seeded random CLIP image tower in open_clip's ``visual.*`` key layout (used when no local checkpoint exists): class embedding and
+    position table at open_clip's scale (width ** -0.5), a bias-free patch convolution, ``ln_pre`` with gains spread around 1 and
+    non-zero biases (so that it really acts), blocks with non-trivial LayerNorm affines and biases, plus ``ln_post`` and ``proj`` (loaded, unused here)."""
+    g = torch.Generator().manual_seed(seed)
+    scale = embed_dim ** -0.5
+    sd = {"visual.class_embedding": scale * torch.randn(embed_dim, generator=g),
+          "visual.positional_embedding": scale * torch.randn((img // patch) ** 2 + 1, embed_dim, generator=g)}
+    bound = 1.0 / math.sqrt(in_chans * patch * patch)
+    sd["visual.conv1.weight"] = (torch.rand(embed_dim, in_chans, patch, patch, generator=g) * 2 - 1) * bound
+    sd["visual.ln_pre.weight"] = 1.0 + 0.25 * torch.randn(embed_dim, generator=g)
+    sd["visual.ln_pre.bias"] = 0.05 * torch.randn(embed_dim, generator=g)
+    _random_blocks(sd, "visual.transformer.resblocks.", _OPENCLIP_BLOCK, embed_dim, depth, g)
+    sd["visual.ln_post.weight"], sd["visual.ln_post.bias"] = torch.ones(embed_dim), torch.zeros(embed_dim)
+    sd["visual.proj"] = scale * torch.randn(embed_dim, out_dim, generator=g)
+    return sd
+
+
+def random_siglip_state_dict(embed_dim=768, depth=12, patch=16, img=224, seed=0, in_chans=3) -> Dict[str, torch.Tensor]:
+    """Seeded random SigLIP image tower in timm's key layout: no class token, a position table of (img / patch) ** 2 entries, a patch
+    convolution with bias, blocks with non-trivial LayerNorm affines and biases, plus the final ``norm`` and two ``attn_pool`` tensors
+    (loaded, unused here)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {"pos_embed": 0.02 * torch.randn(1, (img // patch) ** 2, embed_dim, generator=g)}
+    bound = 1.0 / math.sqrt(in_chans * patch * patch)
+    sd["patch_embed.proj.weight"] = (torch.rand(embed_dim, in_chans, patch, patch, generator=g) * 2 - 1) * bound
+    sd["patch_embed.proj.bias"] = (torch.rand(embed_dim, generator=g) * 2 - 1) * bound
+    _random_blocks(sd, "blocks.", _TIMM_BLOCK, embed_dim, depth, g)
+    sd["norm.weight"], sd["norm.bias"] = torch.ones(embed_dim), torch.zeros(embed_dim)
+    sd["attn_pool.latent"] = 0.02 * torch.randn(1, 1, embed_dim, generator=g)
+    sd["attn_pool.norm.weight"] = torch.ones(embed_dim)
+    return sd
+
+
+def _rename_blocks(out, sd, src_prefix, src_names, dst_prefix, dst_names):
+    i = 0
+    while f"{src_prefix}{i}.{src_names['norm1']}.weight" in sd:
+        s, d = f"{src_prefix}{i}.", f"{dst_prefix}{i}."
+        for n in ("norm1", "norm2", "proj", "fc1", "fc2"):
+            for t in (".weight", ".bias"):
+                out[d + dst_names[n] + t] = sd[s + src_names[n] + t]
+        out[d + dst_names["qkv_w"]], out[d + dst_names["qkv_b"]] = sd[s + src_names["qkv_w"]], sd[s + src_names["qkv_b"]]
+        i += 1
+    return i
+
+
+def openclip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """open_clip's CLIP state dict (``visual.*``; the bare image tower without the prefix too) -> the keys the engine reads.  ``ln_post``
+    and ``proj`` (the projection head, not on the tap path: clip.py:67-101) and everything outside the image tower are dropped."""
+    pre = "visual." if any(k.startswith("visual.") for k in sd) else ""
+    v = {k[len(pre):]: t for k, t in sd.items() if k.startswith(pre)}
+    out = {"cls_token": v["class_embedding"].reshape(1, 1, -1), "pos_embed": v["positional_embedding"].unsqueeze(0),
+           "patch_embed.proj.weight": v["conv1.weight"], "norm_pre.weight": v["ln_pre.weight"], "norm_pre.bias": v["ln_pre.bias"]}
+    _rename_blocks(out, v, "transformer.resblocks.", _OPENCLIP_BLOCK, "blocks.", _TIMM_BLOCK)
+    return out
+
+
+def engine_to_openclip(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of openclip_to_engine (``visual.*`` keys; no ``ln_post`` / ``proj``)."""
+    out = {"class_embedding": sd["cls_token"].reshape(-1), "positional_embedding": sd["pos_embed"][0], "conv1.weight": sd["patch_embed.proj.weight"],
+           "ln_pre.weight": sd["norm_pre.weight"], "ln_pre.bias": sd["norm_pre.bias"]}
+    _rename_blocks(out, sd, "blocks.", _TIMM_BLOCK, "transformer.resblocks.", _OPENCLIP_BLOCK)
+    return {"visual." + k: v for k, v in out.items()}
+
+
+def _hf_layers_to_engine(out, g, has):
+    i = 0
+    while has(f"encoder.layers.{i}.layer_norm1.weight"):
+        s, d = f"encoder.layers.{i}.", f"blocks.{i}."
+        for a, b in (("layer_norm1", "norm1"), ("layer_norm2", "norm2"), ("self_attn.out_proj", "attn.proj"), ("mlp.fc1", "mlp.fc1"), ("mlp.fc2", "mlp.fc2")):
+            out[d + b + ".weight"], out[d + b + ".bias"] = g(s + a + ".weight"), g(s + a + ".bias")
+        out[d + "attn.qkv.weight"] = torch.cat([g(s + f"self_attn.{n}_proj.weight") for n in "qkv"], 0)
+        out[d + "attn.qkv.bias"] = torch.cat([g(s + f"self_attn.{n}_proj.bias") for n in "qkv"], 0)
+        i += 1
+
+
+def _engine_layers_to_hf(out, sd):
+    i = 0
+    while f"blocks.{i}.norm1.weight" in sd:
+        s, d = f"blocks.{i}.", f"vision_model.encoder.layers.{i}."
+        for a, b in (("layer_norm1", "norm1"), ("layer_norm2", "norm2"), ("self_attn.out_proj", "attn.proj"), ("mlp.fc1", "mlp.fc1"), ("mlp.fc2", "mlp.fc2")):
+            out[d + a + ".weight"], out[d + a + ".bias"] = sd[s + b + ".weight"], sd[s + b + ".bias"]
+        for n, w, b in zip("qkv", sd[s + "attn.qkv.weight"].chunk(3, 0), sd[s + "attn.qkv.bias"].chunk(3, 0)):
+            out[d + f"self_attn.{n}_proj.weight"], out[d + f"self_attn.{n}_proj.bias"] = w.contiguous(), b.contiguous()
+        i += 1
+
+
+def hf_clip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """transformers' CLIPVisionModel (or CLIPModel) keys -> the engine's; ``post_layernorm``, ``position_ids``, the projection and the text
+    tower are dropped."""
+    pre = next((p for p in ("vision_model.", "") if p + "embeddings.class_embedding" in sd), None)
+    if pre is None:
+        raise KeyError("not a transformers CLIP vision state dict (vision_model.embeddings.class_embedding missing)")
+    g, has = (lambda k: sd[pre + k]), (lambda k: pre + k in sd)
+    out = {"cls_token": g("embeddings.class_embedding").reshape(1, 1, -1), "pos_embed": g("embeddings.position_embedding.weight").unsqueeze(0),
+           "patch_embed.proj.weight": g("embeddings.patch_embedding.weight"),
+           "norm_pre.weight": g("pre_layrnorm.weight"), "norm_pre.bias": g("pre_layrnorm.bias")}
+    _hf_layers_to_engine(out, g, has)
+    return out
+
+
+def engine_to_hf_clip(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of hf_clip_to_engine (CLIPVisionModel keys; no ``post_layernorm``)."""
+    out = {"vision_model.embeddings.class_embedding": sd["cls_token"].reshape(-1), "vision_model.embeddings.position_embedding.weight": sd["pos_embed"][0],
+           "vision_model.embeddings.patch_embedding.weight": sd["patch_embed.proj.weight"],
+           "vision_model.pre_layrnorm.weight": sd["norm_pre.weight"], "vision_model.pre_layrnorm.bias": sd["norm_pre.bias"]}
+    _engine_layers_to_hf(out, sd)
+    return out
+
+
+def hf_siglip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """transformers' SiglipVisionModel (or SiglipModel) keys -> the engine's; ``post_layernorm``, the attention-pool ``head`` and the text
+    tower are dropped."""
+    pre = next((p for p in ("vision_model.", "") if p + "embeddings.patch_embedding.weight" in sd), None)
+    if pre is None:
+        raise KeyError("not a transformers SigLIP vision state dict (vision_model.embeddings.patch_embedding.weight missing)")
+    g, has = (lambda k: sd[pre + k]), (lambda k: pre + k in sd)
+    out = {"pos_embed": g("embeddings.position_embedding.weight").unsqueeze(0),
+           "patch_embed.proj.weight": g("embeddings.patch_embedding.weight"), "patch_embed.proj.bias": g("embeddings.patch_embedding.bias")}
+    _hf_layers_to_engine(out, g, has)
+    return out
+
+
+def engine_to_hf_siglip(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of hf_siglip_to_engine (SiglipVisionModel keys; no ``post_layernorm`` / ``head``)."""
+    out = {"vision_model.embeddings.position_embedding.weight": sd["pos_embed"][0],
+           "vision_model.embeddings.patch_embedding.weight": sd["patch_embed.proj.weight"], "vision_model.embeddings.patch_embedding.bias": sd["patch_embed.proj.bias"]}
+    _engine_layers_to_hf(out, sd)
+    return out
+
+
+def timm_siglip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """timm's SigLIP ViT keys are the engine's own; the attention pool (``attn_pool.*``) and the final ``norm.*`` — neither on the tap path
+    (siglip.py:58-93) — are dropped."""
+    return {k: v for k, v in sd.items() if not (k.startswith("attn_pool.") or k.startswith("norm."))}
+
+
+def clip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Any of the CLIP layouts (open_clip, transformers, or already the engine's)."""
+    if any(k.endswith("embeddings.class_embedding") for k in sd):
+        return hf_clip_to_engine(sd)
+    if "visual.conv1.weight" in sd or "conv1.weight" in sd:
+        return openclip_to_engine(sd)
+    return dict(sd)
+
+
+def siglip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Any of the SigLIP layouts (timm, transformers)."""
+    if any(k.endswith("embeddings.patch_embedding.weight") for k in sd):
+        return hf_siglip_to_engine(sd)
+    return timm_siglip_to_engine(sd)
+
+
 def sincos_pos_embed_2d(embed_dim: int, grid_hw, add_cls_token: bool = True) -> np.ndarray:
     """evals/models/utils.py:75-102 + HF get_2d_sincos_pos_embed_from_grid (MAE): half of the
     channels encode the w coordinate ("w goes first"), half the h coordinate; each half is
@@ -203,7 +393,7 @@ class ViTParams(nn.Module):
                     setattr(mod, p, _Named())
                 mod = getattr(mod, p)
             mod.register_parameter(parts[-1], nn.Parameter(v.clone().float(), requires_grad=False))
-        self.embed_dim = sd["cls_token"].shape[-1]
+        self.embed_dim = sd["cls_token" if "cls_token" in sd else "pos_embed"].shape[-1]
         self.depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
 
     @property
@@ -224,6 +414,7 @@ class ViTBackbone(nn.Module):
     ln_eps = 1e-6
     pos_embed_mode = "dino"
     tap_input_of_block = False
+    act = "gelu"  # after fc1: 'gelu' (erf), 'quick_gelu', 'gelu_tanh' (ViTEngine)
     supports_pipelining = True  # per-slot buffers, tap-BN running-statistics updates deferred to the consumer (mvp/pipeline.py)
     graph_safe = True  # a pipelined forward launches only this library's kernels on fixed buffers: it can be captured in a hipGraph
 
@@ -249,7 +440,7 @@ class ViTBackbone(nn.Module):
         return getattr(self, self.params_attr)
 
     def _signature(self):
-        return tuple((p.data_ptr(), p._version) for p in self._params().parameters()) + (self._precision,)
+        return tuple((p.data_ptr(), p._version) for p in self._params().parameters()) + (self._precision, self.act)
 
     def engine(self) -> ViTEngine:
         sig = self._signature()
@@ -260,7 +451,7 @@ class ViTBackbone(nn.Module):
                 raise lib.MvpError("backbone parameters are on the CPU: call model.to('cuda') — the HIP path has no CPU fallback")
             sd = {k: v for k, v in params.state_dict().items()}
             self._engine_obj = ViTEngine(sd, heads=self.heads, patch=self.patch_size, ln_eps=self.ln_eps, precision=self._precision,
-                                         device=dev, pos_embed_mode=self.pos_embed_mode)
+                                         device=dev, pos_embed_mode=self.pos_embed_mode, act=self.act)
             self.n_prefix = self._engine_obj.n_prefix
             self._engine_sig = sig
         return self._engine_obj

@@ -269,16 +269,19 @@ def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, 
     _TRACE.append(("gemm", tile, precision, 2.0 * M * N * K, e0, e1))
 
 
-def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: Pair, M: int, Cdim: int, eps: float,
+def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: Optional[Pair], M: int, Cdim: int, eps: float,
               out_f32: Optional[torch.Tensor] = None, out_f16: bool = False) -> None:
-    """``out_f16``: the pair is written as the activation operand of a PREC_F16X2 GEMM (``split_f16_comp``'s form)."""
+    """``out_f16``: the pair is written as the activation operand of a PREC_F16X2 GEMM (``split_f16_comp``'s form).
+    ``out`` = None with ``out_f32`` set: fp32 output only; ``out_f32`` may be ``x`` itself (in place: CLIP's ln_pre)."""
     ilv = isinstance(out, IlvPair)
     if ilv:
         out = (out.t, None)
+    elif out is None:
+        out = (None, None)
     a = lib.LayerNormArgs(lib.ptr(x), lib.ptr(gamma), lib.ptr(beta), lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(out_f32), M, Cdim, eps,
                           lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE, 1 if out_f16 else 0)
     # algorithmic HBM bytes: the fp32 row read once + the bf16 pair (or single bf16) written once
-    nb = M * Cdim * (4 + 2 * (2 if (ilv or out[1] is not None) else 1) + (4 if out_f32 is not None else 0))
+    nb = M * Cdim * (4 + (2 * (2 if (ilv or out[1] is not None) else 1) if (ilv or out[0] is not None) else 0) + (4 if out_f32 is not None else 0))
     _traced("hbm", "layernorm_kernel", 0, float(nb), lambda: lib.call("mvp_layernorm_fwd", a))
 
 

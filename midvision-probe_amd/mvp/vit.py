@@ -82,6 +82,7 @@ _PACK_REGISTRY: Dict[int, PackedFeatures] = {}
 # one entry per (pipeline slot, forward shape, batch of the forward): a span pipeline keeps 2 slots x two shapes (floor / ceil of T / B
 # whole batches) x up to 14 batches = 54 entries at B = 8, and a model has a train and an eval pipeline; a graph replay re-registers
 # its packings (pipeline._forward), so an entry that ages out anyway comes back at its forward's next replay
+ACTIVATIONS = {"gelu": lib.ACT_GELU, "quick_gelu": lib.ACT_QUICK_GELU, "gelu_tanh": lib.ACT_GELU_TANH}  # ViTEngine(act=...): after fc1
 ATT_QK_DEFAULT = "auto"  # MVP_ATT_QK: "f16" = Q.K^T in two f16 products (ViTEngine.att_qk_f16), "pair" = three bf16 products, "auto" = f16 for f16x2 engines
 _PACK_REGISTRY_MAX = 256
 
@@ -124,11 +125,16 @@ def lookup_pack(maps: Sequence[torch.Tensor]) -> Optional[PackedFeatures]:
 
 class ViTEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, heads: int, patch: int = 16, ln_eps: float = 1e-6,
-                 precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True):
+                 precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True, act: str = "gelu"):
         """``state_dict`` in the DINO / timm layout; DINOv2's extras are picked up from it: ``register_tokens`` [1, R, C] (then
         n_prefix = 1 + R) and ``blocks.i.ls1.gamma`` / ``blocks.i.ls2.gamma`` (LayerScale, fused into the proj / fc2 epilogues).
-        pos_embed_mode: 'dino' (bicubic with the +0.1 scale nudge), 'fixed', or 'dinov2_reg' (bicubic to the grid size, antialiased:
-        DINOv2's register models)."""
+        So are CLIP's and SigLIP's: ``norm_pre.weight`` / ``norm_pre.bias`` (a LayerNorm over the residual stream before block 0, in place),
+        a missing ``patch_embed.proj.bias`` (bias-free patch convolution), a missing ``cls_token`` (no prefix row at all: n_prefix = 0,
+        ``pos_embed`` [1, n, C] without a CLS entry).
+        pos_embed_mode: 'dino' (bicubic with the +0.1 scale nudge), 'fixed', 'dinov2_reg' (bicubic to the grid size, antialiased:
+        DINOv2's register models), or 'resize_aa' (the same resample, applied whenever the table's grid-entry COUNT differs from
+        gh * gw — the reference's resize_pos_embed, evals/models/utils.py:12-52 — with or without a CLS entry).
+        act: the activation after fc1: 'gelu' (erf), 'quick_gelu' (x sigmoid(1.702 x): OpenAI CLIP) or 'gelu_tanh' (SigLIP)."""
         self.device = torch.device(device)
         self.precision = parse_precision(precision)
         # 'f16x2': a bf16x3 engine (buffers, patch embedding, attention, taps) whose four block GEMMs run two products (lib.PREC_F16X2)
@@ -145,16 +151,23 @@ class ViTEngine:
         self.att_qk_f16 = self.att_v_f16 and (qk == "f16" or (qk == "auto" and self.f16x2))
         self.check_f16_range = os.environ.get("MVP_CHECK_F16_RANGE", "0") == "1"  # diagnostic: see _check_f16_range
         self.pos_embed_mode = pos_embed_mode
+        if act not in ACTIVATIONS:
+            raise ValueError(f"unknown activation {act!r} (use one of {sorted(ACTIVATIONS)})")
+        self.act_name, self.act = act, ACTIVATIONS[act]
         sd = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in state_dict.items()}
-        self.C = sd["cls_token"].shape[-1]
+        self.has_cls = "cls_token" in sd
+        self.C = sd["cls_token" if self.has_cls else "pos_embed"].shape[-1]
         if self.C != heads * 64:
             raise lib.MvpError(f"attention kernel requires head_dim 64 (C={self.C}, heads={heads})")
         self.depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
-        self.cls = sd["cls_token"].reshape(-1).contiguous()
-        self.pos_embed = sd["pos_embed"]  # [1, 1+n, C] fp32
+        self.cls = sd["cls_token"].reshape(-1).contiguous() if self.has_cls else None
+        self.pos_embed = sd["pos_embed"]  # [1, 1+n, C] fp32 ([1, n, C] without a CLS token)
         reg = sd.get("register_tokens")
         self.reg = reg.reshape(-1, self.C).contiguous() if reg is not None and reg.numel() else None  # [R, C]
-        self.n_prefix = 1 + (0 if self.reg is None else self.reg.shape[0])
+        if not self.has_cls and self.reg is not None:
+            raise lib.MvpError("register tokens without a cls_token: no model on this path has them")
+        self.n_prefix = (1 + (0 if self.reg is None else self.reg.shape[0])) if self.has_cls else 0
+        self.pre_norm = (sd["norm_pre.weight"], sd["norm_pre.bias"]) if "norm_pre.weight" in sd else None  # CLIP's ln_pre
         pw = sd["patch_embed.proj.weight"]
         self.in_chans = pw.shape[1]
         # patch-embed GEMM depth: C*P*P, padded with zero columns to what the tile kernels take (K % 32 in bf16x3, else K % 64) when the
@@ -166,7 +179,7 @@ class ViTEngine:
         if self.k_patch != kp:
             pw2 = F.pad(pw2, (0, self.k_patch - kp)).contiguous()
         self.w_patch = ops.split_bf16(pw2, self.precision)
-        self.b_patch = sd["patch_embed.proj.bias"]
+        self.b_patch = sd.get("patch_embed.proj.bias")  # (CLIP's patch convolution has none)
         self.blocks = []
         for i in range(self.depth):
             p = f"blocks.{i}."
@@ -261,8 +274,19 @@ class ViTEngine:
         pe = self._pos.get(key)
         if pe is not None:
             return pe
-        n = self.pos_embed.shape[1] - 1
-        if self.pos_embed_mode == "fixed" or (gh * gw == n and dim2 == dim3):
+        c0 = 1 if self.has_cls else 0  # the table's CLS entry
+        n = self.pos_embed.shape[1] - c0
+        if self.pos_embed_mode == "resize_aa":  # the count test, not the shape test
+            if gh * gw == n:
+                pe = self.pos_embed[0].contiguous()
+            else:
+                side = int(n ** 0.5)
+                grid = self.pos_embed[:, c0:].reshape(1, side, side, self.C).permute(0, 3, 1, 2)
+                grid = F.interpolate(grid, size=(gh, gw), mode="bicubic", antialias=True, align_corners=False)
+                pe = torch.cat((self.pos_embed[0, :c0], grid.permute(0, 2, 3, 1).reshape(-1, self.C)), dim=0).contiguous()
+        elif not self.has_cls and self.pos_embed_mode != "fixed":
+            raise lib.MvpError(f"pos_embed_mode {self.pos_embed_mode!r} needs a CLS entry in the table: use 'resize_aa' or 'fixed'")
+        elif self.pos_embed_mode == "fixed" or (gh * gw == n and dim2 == dim3):
             pe = self.pos_embed[0].contiguous()
         elif self.pos_embed_mode == "dinov2_reg":  # DINOv2 register models: interpolate_offset 0, antialias (size = the grid)
             side = int(math.sqrt(n))
@@ -307,12 +331,16 @@ class ViTEngine:
             ops.patch_gather_ld(images, ws["patches"], P, gh, gw, ph // 2, pw // 2, Kp)
         pos = self.pos_for(gh, gw, H + ph, W + pw)
         # x[b, npre+p, :] = patches · Wᵀ + bias + pos[1+p]   (row remap skips the CLS / register slots)
-        ops.gemm(ws["patches"], self.w_patch, B * gh * gw, C, Kp, bias=self.b_patch, residual=pos[1:], out_f32=ws["x"],
+        ops.gemm(ws["patches"], self.w_patch, B * gh * gw, C, Kp, bias=self.b_patch, residual=pos[1:] if self.has_cls else pos, out_f32=ws["x"],
                  precision=self.precision, row_group=gh * gw, row_group_stride=N, row_group_off=npre, res_row_mod=gh * gw)
-        if self.reg is None:
+        if not self.has_cls:
+            pass  # no prefix rows at all (SigLIP)
+        elif self.reg is None:
             ops.cls_rows(self.cls, pos, ws["x"], B, N, C)
         else:
             ops.prefix_rows(self.cls, pos, self.reg, ws["x"], B, N, C)
+        if self.pre_norm is not None:  # CLIP's ln_pre: every row of the residual stream, in place
+            ops.layernorm(ws["x"], self.pre_norm[0], self.pre_norm[1], None, B * N, C, self.ln_eps, out_f32=ws["x"])
         return ws, B, gh, gw
 
     def _check_f16_range(self, what: str, pair, rows: int) -> None:
@@ -349,10 +377,10 @@ class ViTEngine:
         ops.layernorm(x, blk["n2w"], blk["n2b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
         if chk:
             self._check_f16_range(f"block {i}: LayerNorm 2 output", ws["xn"], M)
-        ops.gemm(ws["xn"], blk["fc1_w"], M, self.hidden, C, bias=blk["fc1_b"], out=ws["hmid"], act=lib.ACT_GELU, precision=gp, w_ilv=blk.get("fc1_w_ilv"),
+        ops.gemm(ws["xn"], blk["fc1_w"], M, self.hidden, C, bias=blk["fc1_b"], out=ws["hmid"], act=self.act, precision=gp, w_ilv=blk.get("fc1_w_ilv"),
                  f16_col0=-1 if f2 else 0)
         if chk:
-            self._check_f16_range(f"block {i}: GELU(fc1) output", ws["hmid"], M)
+            self._check_f16_range(f"block {i}: {self.act_name}(fc1) output" if self.act_name != "gelu" else f"block {i}: GELU(fc1) output", ws["hmid"], M)
         ops.gemm(ws["hmid"], blk["fc2_w"], M, C, self.hidden, bias=blk["fc2_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("fc2_w_ilv"),
                  col_scale=blk["ls2"])
 
@@ -375,6 +403,8 @@ class ViTEngine:
         the rows of a trailing incomplete batch are copied to the carry store for the next span.  Returns ``TapGroups`` of the
         (carry + images) // batch batches this forward completes."""
         span = groups if isinstance(groups, pipeline.Span) else None
+        if want_cls and not self.has_cls:
+            raise lib.MvpError("want_cls: this model has no CLS token (n_prefix = 0); use output 'dense' or 'gap'")
         ws, Bt, gh, gw = self.tokens(images, headroom=span.batch if span else 0)
         N, C, hw = self.n_prefix + gh * gw, self.C, gh * gw
         if span is not None:
