@@ -35,7 +35,7 @@ extern "C" {
 
 #define MVP_PREC_BF16 1   /* one bf16 MFMA pass                              */
 #define MVP_PREC_BF16X3 3 /* three passes (split bf16), ~fp32 operand accuracy */
-#define MVP_PREC_F16X2 2  /* (ABI 6, opt-in) TWO fp16 passes per contraction of mvp_gemm_bias_act_res / mvp_gemm_pp (plain linear GEMMs only), with the
+#define MVP_PREC_F16X2 2  /* (ABI 6; the ViT wrappers' default) TWO fp16 passes per contraction of mvp_gemm_bias_act_res / mvp_gemm_pp (plain linear GEMMs only), with the
                              weight's fp16 rounding error carried by the second pass ("compensated" pairs).  With s = 2^-6:
                                activation  a_hi = fp16(a),            a_lo = fp16(8 (a - a_hi) + a_hi / 8)       (LayerNorm / attention out_f16 = 1,
                                                                                                                   a GEMM epilogue's out_f16_col0 = -1)

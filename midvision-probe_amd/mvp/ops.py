@@ -259,14 +259,7 @@ def gemm(a: Pair, w: Pair, M: int, N: int, K: int, *, bias=None, residual=None, 
         name, args = "mvp_gemm_scaled", lib.GemmScaledArgs(args, lib.ptr(col_scale))
     else:
         name = "mvp_gemm_bias_act_res"
-    if _TRACE is None:
-        lib.call(name, args)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    lib.call(name, args)
-    e1.record()
-    _TRACE.append(("gemm", tile, precision, 2.0 * M * N * K, e0, e1))
+    _traced("gemm", tile, precision, 2.0 * M * N * K, lambda: lib.call(name, args))
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: Optional[Pair], M: int, Cdim: int, eps: float,
@@ -299,14 +292,7 @@ def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precis
     a = lib.AttentionArgs(lib.ptr(qkv[0]), lib.ptr(qkv[1]), lib.ptr(out[0]), lib.ptr(out[1]), B, N, H,
                           ld_qkv if ld_qkv is not None else 3 * H * 64, ld_out if ld_out is not None else H * 64, scale, precision,
                           lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE, (2 if qk_f16 else 1) if v_f16 else 0, 1 if out_f16 else 0)
-    if _TRACE is None:
-        lib.call("mvp_attention_fwd", a)
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    lib.call("mvp_attention_fwd", a)
-    e1.record()
-    _TRACE.append(("attention", "4x32q", precision, 4.0 * B * H * N * N * 64, e0, e1))
+    _traced("attention", "4x32q", precision, 4.0 * B * H * N * N * 64, lambda: lib.call("mvp_attention_fwd", a))
 
 
 def cls_rows(cls: torch.Tensor, pos0: torch.Tensor, x: torch.Tensor, B: int, N: int, Cdim: int) -> None:

@@ -463,11 +463,8 @@ class FeaturePipeline:
                 return self._capture(slot, s, batches, shape, G, ent, eng)  # (its replay computed this forward's features)
         self._fill(ent["static_in"], batches, G)
         ent["graph"].replay()
-        from .vit import register_pack
-
         for pk in ent["packs"]:
-            pk.generation += 1  # the host code that counts rewrites of the packing does not run on a replay ...
-            register_pack(pk.source_refs, pk)  # ... nor does the registration: an entry aged out of the registry (other pipelines' packings) comes back
+            pk.rewritten()  # (the forward's host code, which says so for an eager forward, does not run on a replay)
         return ent["feats"], ent["deferred"]
 
     def _precapture_spans(self, s, sample: torch.Tensor) -> None:

@@ -20,19 +20,22 @@ from __future__ import annotations
 
 import math
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import lib, ops, pipeline
+from .buffers import EngineBuffers
 from .lib import PREC_BF16, PREC_BF16X3
 
 
 def parse_precision(p) -> int:
-    """'bf16x3' (default: three bf16 products per contraction, ~1e-5 on the features), 'f16x2' (opt-in: the four GEMMs of every block
+    """'bf16x3' (three bf16 products per contraction, ~1e-5 on the features), 'f16x2' (the four GEMMs of every block
     with two fp16 products over compensated fp16 pairs, include/mvp_hip.h MVP_PREC_F16X2; everything else as in bf16x3; the same
-    ~1e-5 on the features, |activation| <= 65504), 'bf16' (one product: fails the 1e-3 feature contract)."""
+    ~1e-5 on the features, |activation| <= 65504), 'bf16' (one product: fails the 1e-3 feature contract).  The ViT wrappers run
+    'f16x2' unless told otherwise (backbone.default_precision()); a bare ViTEngine(...) without ``precision`` is a 'bf16x3' engine."""
     if p in (PREC_BF16, PREC_BF16X3, lib.PREC_F16X2):
         return p
     s = str(p).lower()
@@ -59,6 +62,11 @@ class PackedFeatures:
     """Token-major operand of the linear-probe GEMMs: F [Mpad, Cpad] bf16 pair (forward: F·Wᵀ by the NT GEMM;
     weight gradient: gᵀ·F by the TN split-K kernel, which reads the same row-major image through transposed LDS reads)."""
 
+    @staticmethod
+    def padded(B, h, w, Ctot):
+        """(Mpad, Cpad) of a packing: NT GEMM K % 64, TN kernel Cin % 128; pad rows / columns stay zero."""
+        return (B * h * w + 63) // 64 * 64, (Ctot + 127) // 128 * 128
+
     def __init__(self, B, h, w, Ctot, precision, device, tok=None):
         self.B, self.h, self.w, self.Ctot, self.precision = B, h, w, Ctot, precision
         self.M = B * h * w
@@ -68,15 +76,15 @@ class PackedFeatures:
         self.sources: List[Tuple[int, int]] = []  # (data_ptr, _version) of the NCHW maps packed here
         self.source_refs: List[torch.Tensor] = []  # the maps themselves: while they live, their addresses cannot be recycled
         self.generation = 0  # bumped every time the buffers are rewritten (they are reused across steps)
+        self.registry_key: Optional[int] = None  # where register_pack last entered this packing
         self.scratch: Dict[str, object] = {}  # per-shape scratch of the head backward (zero-padded once)
 
+    def rewritten(self, maps: Optional[Sequence[torch.Tensor]] = None) -> None:
+        """The buffers now hold the features of ``maps`` (None: of the same maps again — a graph replay, which runs none of the forward's
+        host code): count the rewrite and (re-)enter the registry (an entry aged out by other pipelines' packings comes back)."""
+        self.generation += 1
+        register_pack(self.source_refs if maps is None else maps, self)
 
-def _padded(B, h, w, Ctot):
-    """(Mpad, Cpad) of a packing: NT GEMM K % 64, TN kernel Cin % 128; pad rows / columns stay zero."""
-    return (B * h * w + 63) // 64 * 64, (Ctot + 127) // 128 * 128
-
-
-PackedFeatures.padded = staticmethod(_padded)
 
 _PACK_REGISTRY: Dict[int, PackedFeatures] = {}
 # one entry per (pipeline slot, forward shape, batch of the forward): a span pipeline keeps 2 slots x two shapes (floor / ceil of T / B
@@ -102,9 +110,10 @@ def register_pack(maps: Sequence[torch.Tensor], pack: PackedFeatures) -> None:
     pack.source_refs = list(maps)
     # one entry per packing buffer: the probe consumes features right after the backbone, or — with several forwards in flight
     # (mvp/pipeline.py) — one entry per pipeline slot.  Entries of other engines / shapes age out beyond the newest few.
-    for k in [k for k, v in _PACK_REGISTRY.items() if v is pack]:
-        del _PACK_REGISTRY[k]
-    _PACK_REGISTRY[maps[0].data_ptr()] = pack
+    if _PACK_REGISTRY.get(pack.registry_key) is pack:
+        del _PACK_REGISTRY[pack.registry_key]
+    pack.registry_key = maps[0].data_ptr()
+    _PACK_REGISTRY[pack.registry_key] = pack
     while len(_PACK_REGISTRY) > _PACK_REGISTRY_MAX:
         del _PACK_REGISTRY[next(iter(_PACK_REGISTRY))]
 
@@ -123,6 +132,23 @@ def lookup_pack(maps: Sequence[torch.Tensor]) -> Optional[PackedFeatures]:
     return pack
 
 
+def plan_taps(Bt: int, groups) -> Tuple[int, int, int, int]:
+    """(G, B, carry, tail) of a forward over ``Bt`` images (ViTEngine.forward_taps): its taps complete G batches of B images, the first
+    of them together with the ``carry`` images the previous span ended in, and leave the ``tail`` images of a cut batch to the next
+    span: carry + Bt == G * B + tail.  ``groups``: G equal batches (no carry, no tail) or a ``pipeline.Span``."""
+    if not isinstance(groups, pipeline.Span):
+        if groups < 1 or Bt % groups:
+            raise lib.MvpError(f"grouped forward: {Bt} images do not split into {groups} equal batches")
+        return groups, Bt // groups, 0, 0
+    B, carry = int(groups.batch), int(groups.carry)
+    if B < 1 or not 0 <= carry < B:
+        raise lib.MvpError(f"span forward: carry {carry} outside [0, {B})")
+    G, tail = divmod(carry + Bt, B)
+    if G < 1:
+        raise lib.MvpError(f"span forward: {carry} + {Bt} images complete no batch of {B}")
+    return G, B, carry, tail
+
+
 class ViTEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, heads: int, patch: int = 16, ln_eps: float = 1e-6,
                  precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True, act: str = "gelu"):
@@ -131,6 +157,7 @@ class ViTEngine:
         So are CLIP's and SigLIP's: ``norm_pre.weight`` / ``norm_pre.bias`` (a LayerNorm over the residual stream before block 0, in place),
         a missing ``patch_embed.proj.bias`` (bias-free patch convolution), a missing ``cls_token`` (no prefix row at all: n_prefix = 0,
         ``pos_embed`` [1, n, C] without a CLS entry).
+        precision: ``parse_precision``; 'bf16x3' when not given — the wrappers always give theirs (backbone.default_precision(): 'f16x2').
         pos_embed_mode: 'dino' (bicubic with the +0.1 scale nudge), 'fixed', 'dinov2_reg' (bicubic to the grid size, antialiased:
         DINOv2's register models), or 'resize_aa' (the same resample, applied whenever the table's grid-entry COUNT differs from
         gh * gw — the reference's resize_pos_embed, evals/models/utils.py:12-52 — with or without a CLS entry).
@@ -201,42 +228,13 @@ class ViTEngine:
                     blk[n + "_ilv"] = ops.interleave_pair(blk[n])
             self.blocks.append(blk)
         self.hidden = self.blocks[0]["fc1_b"].numel()
-        self._ws: Dict[Tuple[int, int, int, int], dict] = {}  # (B, gh, gw, pipeline slot)
+        self._buffers = EngineBuffers()  # everything a forward reuses, per pipeline slot (mvp/buffers.py)
         self._pos: Dict[Tuple[int, int], torch.Tensor] = {}
-        self._packs: Dict[Tuple[int, int, int, int, int], PackedFeatures] = {}
-        self._slot_outs: Dict[tuple, dict] = {}  # output maps of pipelined forwards, owned by the slot
-        self._ns_lru: List[int] = []  # pipeline namespaces, least recently used first (see _touch_namespace)
-        self._carry: Dict[tuple, torch.Tensor] = {}  # (stream, batch, gh, gw, taps) -> [taps, batch * N, C] tap-level rows of a batch cut by a span's end
         pipeline.publish()  # the split weights are read by forwards on any stream
 
     # ------------------------------------------------------------------ helpers
-    def _touch_namespace(self) -> None:
-        """Slot keys are (pipeline namespace, slot index): every FeaturePipeline owns its buffer sets, so two pipelines over this
-        backbone (a training loop suspended with forwards in flight, a validation pass) never write each other's.  A loop that builds
-        a new pipeline per epoch would otherwise pile the sets up: keep those of the two most recently used namespaces (a captured
-        graph holds on to its own slot's buffers whatever happens here)."""
-        slot = pipeline.current_slot()
-        ns = slot[0] if isinstance(slot, tuple) else None
-        if ns is None or (self._ns_lru and self._ns_lru[-1] == ns):
-            return
-        if ns in self._ns_lru:
-            self._ns_lru.remove(ns)
-        self._ns_lru.append(ns)
-        if len(self._ns_lru) > 2:
-            dead = set(self._ns_lru[:-2])
-            self._ns_lru = self._ns_lru[-2:]
-            gone = lambda k: isinstance(k[-1], tuple) and k[-1][0] in dead  # noqa: E731
-            self._ws = {k: v for k, v in self._ws.items() if not gone(k)}
-            self._packs = {k: v for k, v in self._packs.items() if not gone(k)}
-            self._slot_outs = {k: v for k, v in self._slot_outs.items() if not gone(k)}
-
     def _workspace(self, B: int, gh: int, gw: int, headroom: int = 0) -> dict:
-        self._touch_namespace()
-        key = (B, gh, gw, pipeline.current_slot())
-        ws = self._ws.get(key)
-        if ws is not None and ws["headroom"] < headroom:
-            ws = None
-        if ws is None:
+        def alloc():
             N = self.n_prefix + gh * gw
             M = B * N
             C, dev, pr = self.C, self.device, self.precision
@@ -247,7 +245,7 @@ class ViTEngine:
             ilv = (pr == PREC_BF16X3 and os.environ.get("MVP_ILV", "1") != "0" and C % 32 == 0 and self.hidden % 32 == 0 and
                    all(ops.gemm_tile(M, n, k, gp, 1, pipeline.tile_policy()).startswith("pp ") for n, k in ((3 * C, C), (C, C), (self.hidden, C), (C, self.hidden))))
             xfull = torch.empty(M + headroom * N, C, dtype=torch.float32, device=dev)
-            ws = dict(
+            return dict(
                 xfull=xfull, headroom=headroom, x=xfull[headroom * N:],
                 xn=ops.IlvPair(M, C, dev) if ilv else ops.empty_pair((M, C), pr, dev),
                 qkv=ops.empty_pair((M, 3 * C), pr, dev),
@@ -255,16 +253,15 @@ class ViTEngine:
                 hmid=ops.IlvPair(M, self.hidden, dev) if ilv else ops.empty_pair((M, self.hidden), pr, dev),
                 patches=ops.empty_pair((B * gh * gw, self.k_patch), pr, dev),
             )
-            self._ws = {k: v for k, v in self._ws.items() if k[:3] == key[:3]}  # keep one resolution resident (one buffer set per slot)
-            self._ws[key] = ws
-        return ws
 
-    def slot_state(self, slot: int) -> list:
+        return self._buffers.workspace((B, gh, gw), headroom, alloc)
+
+    def slot_state(self, slot) -> list:
         """Every buffer set this engine currently keeps for pipeline slot ``slot`` (activation workspaces, feature packings, output
-        maps).  A captured hipGraph of that slot's forward holds their raw addresses: the pipeline keeps this list alive with the
-        graph, because the engine itself drops the buffers of other resolutions when a new one arrives."""
-        return ([v for k, v in self._ws.items() if k[-1] == slot] + [v for k, v in self._packs.items() if k[-1] == slot]
-                + [v for k, v in self._slot_outs.items() if k[-1] == slot] + list(self._pos.values()) + list(self._carry.values()))
+        maps), the carry stores and the position tables.  A captured hipGraph of that slot's forward holds their raw addresses: the
+        pipeline keeps this list alive with the graph, because the engine itself drops the buffers of other resolutions when a new one
+        arrives."""
+        return self._buffers.snapshot(slot) + list(self._pos.values())
 
     def pos_for(self, gh: int, gw: int, dim2: int, dim3: int) -> torch.Tensor:
         """Pos-embed for a gh x gw grid.  'dino': bicubic resize with the +0.1 scale nudge of
@@ -276,30 +273,27 @@ class ViTEngine:
             return pe
         c0 = 1 if self.has_cls else 0  # the table's CLS entry
         n = self.pos_embed.shape[1] - c0
+
+        def resampled(expect=None, **how):
+            """The table with its grid entries resampled and the CLS entry re-attached.  ``how`` goes to F.interpolate untouched: torch's
+            bicubic is not bit-stable across ``size`` / ``scale_factor`` (nor antialias / align_corners), so each rule names its own."""
+            side = int(math.sqrt(n))
+            grid = self.pos_embed[:, c0:].reshape(1, side, side, self.C).permute(0, 3, 1, 2)
+            grid = F.interpolate(grid, mode="bicubic", **how)
+            assert expect is None or expect == tuple(grid.shape[-2:])
+            return torch.cat((self.pos_embed[0, :c0], grid.permute(0, 2, 3, 1).reshape(-1, self.C)), dim=0).contiguous()
+
         if self.pos_embed_mode == "resize_aa":  # the count test, not the shape test
-            if gh * gw == n:
-                pe = self.pos_embed[0].contiguous()
-            else:
-                side = int(n ** 0.5)
-                grid = self.pos_embed[:, c0:].reshape(1, side, side, self.C).permute(0, 3, 1, 2)
-                grid = F.interpolate(grid, size=(gh, gw), mode="bicubic", antialias=True, align_corners=False)
-                pe = torch.cat((self.pos_embed[0, :c0], grid.permute(0, 2, 3, 1).reshape(-1, self.C)), dim=0).contiguous()
+            pe = self.pos_embed[0].contiguous() if gh * gw == n else resampled(size=(gh, gw), antialias=True, align_corners=False)
         elif not self.has_cls and self.pos_embed_mode != "fixed":
             raise lib.MvpError(f"pos_embed_mode {self.pos_embed_mode!r} needs a CLS entry in the table: use 'resize_aa' or 'fixed'")
         elif self.pos_embed_mode == "fixed" or (gh * gw == n and dim2 == dim3):
             pe = self.pos_embed[0].contiguous()
         elif self.pos_embed_mode == "dinov2_reg":  # DINOv2 register models: interpolate_offset 0, antialias (size = the grid)
-            side = int(math.sqrt(n))
-            grid = self.pos_embed[:, 1:].reshape(1, side, side, self.C).permute(0, 3, 1, 2)
-            grid = F.interpolate(grid, size=(dim2 // self.patch, dim3 // self.patch), mode="bicubic", antialias=True)
-            pe = torch.cat((self.pos_embed[0, :1], grid.permute(0, 2, 3, 1).reshape(-1, self.C)), dim=0).contiguous()
+            pe = resampled(size=(dim2 // self.patch, dim3 // self.patch), antialias=True)
         else:
-            side = int(math.sqrt(n))
             w0, h0 = dim2 // self.patch + 0.1, dim3 // self.patch + 0.1
-            grid = self.pos_embed[:, 1:].reshape(1, side, side, self.C).permute(0, 3, 1, 2)
-            grid = F.interpolate(grid, scale_factor=(w0 / math.sqrt(n), h0 / math.sqrt(n)), mode="bicubic")
-            assert int(w0) == grid.shape[-2] and int(h0) == grid.shape[-1]
-            pe = torch.cat((self.pos_embed[0, :1], grid.permute(0, 2, 3, 1).reshape(-1, self.C)), dim=0).contiguous()
+            pe = resampled(scale_factor=(w0 / math.sqrt(n), h0 / math.sqrt(n)), expect=(int(w0), int(h0)))
         self._pos[key] = pe
         pipeline.publish()
         return pe
@@ -350,23 +344,30 @@ class ViTEngine:
             if not bool((t.view(torch.float16).abs() < 65504.0).all()):  # (NaN fails the comparison too)
                 raise lib.MvpError(f"f16x2: {what} holds values beyond fp16's range (|v| >= 65504): run this model with precision='bf16x3' (MVP_PRECISION=bf16x3)")
 
+    def _ln1_qkv(self, i: int, ws: dict, M: int, out_f32: Optional[torch.Tensor] = None) -> None:
+        """LayerNorm 1 and the fused qkv projection of block i, into ws['qkv'] in the forms the attention kernel reads — or, with
+        ``out_f32`` (last_block_qkv: no attention follows), as plain fp32 [M, 3C] without any f16 output form."""
+        blk, C, f2 = self.blocks[i], self.C, self.f16x2
+        ops.layernorm(ws["x"], blk["n1w"], blk["n1b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
+        # bf16x3: the V third of qkv leaves the GEMM as hi = fp16, lo = bf16, and the attention kernel holds its probabilities as one
+        # fp16 value (csrc/attention.hip, VF16; MVP_ATT_V=pair brings back the bf16-pair probabilities of rounds 1-3)
+        # (f16x2: Q and K leave as compensated fp16 pairs too — activation / weight-side form, Q.K^T in two f16 products — unless MVP_ATT_QK=pair;
+        #  the attention output, LayerNorm's and fc1's output leave as compensated fp16 activation pairs)
+        pairs = out_f32 is None
+        ops.gemm(ws["xn"], blk["qkv_w"], M, 3 * C, C, bias=blk["qkv_b"], out=ws["qkv"] if pairs else None, out_f32=out_f32,
+                 precision=lib.PREC_F16X2 if f2 else self.precision, w_ilv=blk.get("qkv_w_ilv"),
+                 f16_col0=(-2 * C if self.att_qk_f16 else 2 * C) if (pairs and self.att_v_f16) else 0)
+
     def run_block(self, i: int, ws: dict, B: int, N: int) -> None:
         blk, C, M, pr = self.blocks[i], self.C, B * N, self.precision
         f2 = self.f16x2
         chk = f2 and self.check_f16_range
         gp = lib.PREC_F16X2 if f2 else pr  # precision of the four block GEMMs
         x = ws["x"]
-        ops.layernorm(x, blk["n1w"], blk["n1b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
-        if chk:
+        vf16, qk16 = self.att_v_f16, self.att_qk_f16
+        self._ln1_qkv(i, ws, M)
+        if chk:  # (after the projection: ws["xn"] still holds LayerNorm 1's output)
             self._check_f16_range(f"block {i}: LayerNorm 1 output", ws["xn"], M)
-        # bf16x3: the V third of qkv leaves the GEMM as hi = fp16, lo = bf16, and the attention kernel holds its probabilities as one
-        # fp16 value (csrc/attention.hip, VF16; MVP_ATT_V=pair brings back the bf16-pair probabilities of rounds 1-3)
-        vf16 = self.att_v_f16
-        # (f16x2: Q and K leave as compensated fp16 pairs too — activation / weight-side form, Q.K^T in two f16 products — unless MVP_ATT_QK=pair;
-        #  the attention output, LayerNorm's and fc1's output leave as compensated fp16 activation pairs)
-        qk16 = self.att_qk_f16
-        ops.gemm(ws["xn"], blk["qkv_w"], M, 3 * C, C, bias=blk["qkv_b"], out=ws["qkv"], precision=gp, w_ilv=blk.get("qkv_w_ilv"),
-                 f16_col0=(-2 * C if qk16 else 2 * C) if vf16 else 0)
         if chk and qk16:
             self._check_f16_range(f"block {i}: Q / K", (ws["qkv"][0][:, :2 * C], ws["qkv"][1][:, :2 * C]), M)
         ops.attention(ws["qkv"], ws["ao"], B, N, self.heads, 64 ** -0.5, pr, v_f16=vf16, qk_f16=qk16, out_f16=f2)
@@ -398,126 +399,106 @@ class ViTEngine:
         ``groups`` = ``pipeline.Span(batch, carry)``: the forward's images are a SPAN of the image stream that need not start or end on
         a batch boundary (batches of ``batch`` images; the first ``batch - carry`` images complete the batch whose first ``carry``
         images ended the previous span, when carry > 0).  The blocks do not care; per tap, the carried images' rows (kept in
-        ``self._carry``, written by the previous span's forward on the same stream) are copied in FRONT of this span's rows — the
+        the stream's carry store, written by the previous span's forward on the same stream) are copied in FRONT of this span's rows — the
         ``x`` workspace has that head-room — so that all complete batches are contiguous and one grouped tap-BN launch serves them, and
         the rows of a trailing incomplete batch are copied to the carry store for the next span.  Returns ``TapGroups`` of the
         (carry + images) // batch batches this forward completes."""
-        span = groups if isinstance(groups, pipeline.Span) else None
         if want_cls and not self.has_cls:
             raise lib.MvpError("want_cls: this model has no CLS token (n_prefix = 0); use output 'dense' or 'gap'")
-        ws, Bt, gh, gw = self.tokens(images, headroom=span.batch if span else 0)
-        N, C, hw = self.n_prefix + gh * gw, self.C, gh * gw
-        if span is not None:
-            B, carry = int(span.batch), int(span.carry)
-            if B < 1 or not 0 <= carry < B:
-                raise lib.MvpError(f"span forward: carry {carry} outside [0, {B})")
-            G, tail = (carry + Bt) // B, (carry + Bt) % B
-            if G < 1:
-                raise lib.MvpError(f"span forward: {carry} + {Bt} images complete no batch of {B}")
-            x_bn = ws["xfull"][(ws["headroom"] - carry) * N:]  # the complete batches: carried rows (copied per tap) + this span's rows
-            ckey = (span.stream, B, gh, gw, len(list(layers)))  # one store per image stream (pipeline): see pipeline.Span
-            store = self._carry.get(ckey)
-            if store is None:
-                for k in [k for k in self._carry if k[0] == span.stream]:
-                    del self._carry[k]  # the stream changed shape: its old store has no reader left (captured graphs keep theirs alive)
-                for k in [k for k in self._carry if k[0] not in self._ns_lru]:
-                    del self._carry[k]  # (streams of pipelines whose buffer sets were dropped too: _touch_namespace)
-                store = self._carry[ckey] = torch.empty(len(list(layers)), B * N, C, dtype=torch.float32, device=self.device)
-        else:
-            if groups < 1 or Bt % groups:
-                raise lib.MvpError(f"grouped forward: {Bt} images do not split into {groups} equal batches")
-            G, B, carry, tail = groups, Bt // groups, 0, 0
-            x_bn = ws["x"]
+        span = groups if isinstance(groups, pipeline.Span) else None
         layers = list(layers)
-        outs_g = [TapOutputs() for _ in range(G)]
-        bn_ws = ws.get(("bn_ws", G))  # tap-BN partials + scale / shift of G batches of B * N rows
-        if bn_ws is None:
-            bn_ws = ws[("bn_ws", G)] = torch.empty(G * ops.bn_tokens_workspace_bytes(B * N, C) // 4 + 16, dtype=torch.float32, device=self.device)
-        packed_g = [None] * G
-        if pack:  # reuse the (zero padded) packing buffers across steps: only the valid region is rewritten
-            pkey = (B, gh, gw, len(layers), G, pipeline.current_slot())
-            packs = self._packs.get(pkey)
-            if packs is None:
-                Mpad, Cpad = PackedFeatures.padded(B, gh, gw, C * len(layers))
-                big = ops.zeros_pair((G, Mpad, Cpad), self.precision, self.device)  # one allocation: the tap kernel writes all batches in one launch
-                packs = [PackedFeatures(B, gh, gw, C * len(layers), self.precision, self.device,
-                                        tok=(big[0][g], big[1][g] if big[1] is not None else None)) for g in range(G)]
-                self._packs = {k: v for k, v in self._packs.items() if k[:4] == pkey[:4]}
-                self._packs[pkey] = packs
-            for g in range(G):
-                packs[g].generation += 1
-            packed_g = list(packs)
-        # Plain calls return freshly allocated maps (the caller may keep them).  A pipelined forward (mvp/pipeline.py) writes into
-        # buffers owned by its slot instead — valid until the slot's next forward, which is the pipeline's contract — so the
-        # steady state allocates nothing and no block ever changes hands between the side stream's and the trainer's allocator pools.
-        def new_out():
-            return dict(stats=torch.empty(G, len(layers), 3 * C, dtype=torch.float32, device=self.device),
-                        nchw=[torch.empty(G, B, C, gh, gw, dtype=torch.float32, device=self.device) for _ in layers],
-                        cls=[torch.empty(G, B, C, dtype=torch.float32, device=self.device) if want_cls else None for _ in layers])
-
-        if pipeline.pipelined():
-            okey = (B, gh, gw, tuple(layers), bool(want_cls), G, pipeline.current_slot())
-            out = self._slot_outs.get(okey)
-            if out is None:
-                out = new_out()
-                self._slot_outs = {k: v for k, v in self._slot_outs.items() if k[:5] == okey[:5]}
-                self._slot_outs[okey] = out
-        else:
-            out = new_out()
-        for o in outs_g:
-            o.cls = []
-
+        G, B, carry, tail = plan_taps(images.shape[0], groups)
         # Train-mode tap BN updates its running statistics in place: the only state a frozen forward mutates.  Forwards in flight on
         # different streams finish in any order, so a pipelined forward leaves that update to the consumer (pipeline.defer), which
         # applies it on the trainer's stream in batch order — same arithmetic, same bits (mvp_bn_running_update).
         defer = bn is not None and bn_mode == 0 and pipeline.pipelined()
         if (G > 1 or span is not None) and bn is not None and bn_mode == 0 and not defer:
             raise lib.MvpError("a grouped forward with train-mode tap BN must run under the pipeline (its running-statistics updates are per batch)")
-
-        running = [[] for _ in range(G)]  # per batch of the group: its taps' deferred running-statistics updates
-
-        def tap(j):
-            b = bn[j] if bn is not None else None
-            nchw, cls = out["nchw"][j], out["cls"][j]
-            tok0 = packed_g[0].tok if pack else None
-            if carry:
-                x_bn[:carry * N].copy_(store[j, :carry * N])
-            if tail:
-                store[j, :tail * N].copy_(ws["x"][(Bt - tail) * N:Bt * N])
-            # ONE call for all batches of the group: statistics, normalisation and outputs per batch (mvp_bn_tokens_args.groups)
-            ops.bn_tokens_to_nchw(
-                x_bn, B, N, C, hw, workspace=bn_ws, stats=out["stats"][0, j],
-                gamma=b["weight"] if b else None, beta=b["bias"] if b else None,
-                running_mean=b["running_mean"] if b else None, running_var=b["running_var"] if b else None,
-                nchw=nchw[0], tok=tok0, ld_tok=packed_g[0].Cpad if pack else 0, col_off=j * C,
-                mode=bn_mode, cls_out=cls[0] if want_cls else None, num_batches_tracked=b.get("num_batches_tracked") if b else None, defer_running=defer,
-                groups=G, stats_gstride=out["stats"].stride(0), nchw_gstride=nchw.stride(0),
-                tok_gstride=(packed_g[0].Mpad * packed_g[0].Cpad) if pack else 0, cls_gstride=cls.stride(0) if want_cls else 0)
-            for g in range(G):
-                if want_cls:
-                    outs_g[g].cls.append(cls[g])
-                if defer and b is not None and b.get("running_mean") is not None:
-                    running[g].append((out["stats"][g, j], b["running_mean"], b["running_var"], b.get("num_batches_tracked"), C))
-                outs_g[g].append(nchw[g])
-
+        ws, Bt, gh, gw = self.tokens(images, headroom=span.batch if span else 0)
+        N = self.n_prefix + gh * gw
+        x_bn, store, bn_ws, packs, out = self._tap_buffers(ws, span, G, B, carry, gh, gw, layers, pack, want_cls)
+        t = SimpleNamespace(ws=ws, x_bn=x_bn, store=store, bn_ws=bn_ws, packs=packs, out=out, Bt=Bt, N=N, hw=gh * gw, G=G, B=B, carry=carry, tail=tail,
+                            bn=bn, bn_mode=bn_mode, want_cls=want_cls, defer=defer, outs=[TapOutputs() for _ in range(G)],
+                            running=[[] for _ in range(G)])  # per batch of the group: its taps' deferred running-statistics updates
+        for o in t.outs:
+            o.cls = []
         for i in range(self.depth):
             if tap_input_of_block and i in layers:
-                tap(layers.index(i))
-                if len(outs_g[0]) == len(layers):
+                self._tap(t, layers.index(i))
+                if len(t.outs[0]) == len(layers):
                     break
             self.run_block(i, ws, Bt, N)
             if (not tap_input_of_block) and i in layers:
-                tap(layers.index(i))
-                if len(outs_g[0]) == len(layers):
+                self._tap(t, layers.index(i))
+                if len(t.outs[0]) == len(layers):
                     break
+        for g, o in enumerate(t.outs):
+            if t.running[g]:  # all taps of a batch in ONE launch on the consumer's stream (mvp_bn_running_update_n; the modules are distinct)
+                pipeline.defer(lambda items=t.running[g]: ops.bn_running_update_many(items), group=g)
+            o.stats = t.out["stats"][g]
+            if t.packs is not None:
+                o.packed = t.packs[g]
+                t.packs[g].rewritten(o)
+        return t.outs[0] if (G == 1 and span is None) else TapGroups(t.outs)
+
+    def _tap_buffers(self, ws: dict, span, G: int, B: int, carry: int, gh: int, gw: int, layers: List[int], pack: bool, want_cls: bool):
+        """What the taps of a forward over G batches of B images read and write, from the engine's store (the steady state allocates
+        nothing): ``x_bn`` the rows of the complete batches, ``store`` the span's carry store, ``bn_ws`` the tap-BN scratch, ``packs``
+        the G packings (None without ``pack``), ``out`` the output maps."""
+        N, C, dev, taps = self.n_prefix + gh * gw, self.C, self.device, len(layers)
+        x_bn, store = ws["x"], None
+        if span is not None:
+            x_bn = ws["xfull"][(ws["headroom"] - carry) * N:]  # the complete batches: carried rows (copied per tap) + this span's rows
+            # [taps, B * N, C] tap-level rows of a batch cut by a span's end; one store per image stream (pipeline): see pipeline.Span
+            store = self._buffers.carry(span.stream, (B, gh, gw, taps), lambda: torch.empty(taps, B * N, C, dtype=torch.float32, device=dev))
+        bn_ws = ws.get(("bn_ws", G))  # tap-BN partials + scale / shift of G batches of B * N rows
+        if bn_ws is None:
+            bn_ws = ws[("bn_ws", G)] = torch.empty(G * ops.bn_tokens_workspace_bytes(B * N, C) // 4 + 16, dtype=torch.float32, device=dev)
+
+        def new_packs():
+            Mpad, Cpad = PackedFeatures.padded(B, gh, gw, C * taps)
+            big = ops.zeros_pair((G, Mpad, Cpad), self.precision, dev)  # one allocation: the tap kernel writes all batches in one launch
+            return [PackedFeatures(B, gh, gw, C * taps, self.precision, dev, tok=(big[0][g], big[1][g] if big[1] is not None else None))
+                    for g in range(G)]
+
+        def new_out():
+            return dict(stats=torch.empty(G, taps, 3 * C, dtype=torch.float32, device=dev),
+                        nchw=[torch.empty(G, B, C, gh, gw, dtype=torch.float32, device=dev) for _ in layers],
+                        cls=[torch.empty(G, B, C, dtype=torch.float32, device=dev) if want_cls else None for _ in layers])
+
+        # reuse the (zero padded) packing buffers across steps: only the valid region is rewritten
+        packs = self._buffers.packings((B, gh, gw, taps), G, new_packs) if pack else None
+        # Plain calls return freshly allocated maps (the caller may keep them).  A pipelined forward (mvp/pipeline.py) writes into
+        # buffers owned by its slot instead — valid until the slot's next forward, which is the pipeline's contract — so the
+        # steady state allocates nothing and no block ever changes hands between the side stream's and the trainer's allocator pools.
+        out = self._buffers.outputs((B, gh, gw, tuple(layers), bool(want_cls)), G, new_out) if pipeline.pipelined() else new_out()
+        return x_bn, store, bn_ws, packs, out
+
+    def _tap(self, t, j: int) -> None:
+        """Tap j of the forward ``t`` (forward_taps), on the residual stream as it stands: complete the cut batches through the carry
+        store, then ONE tap-BN launch for all batches; collects every batch's outputs and deferred running-statistics updates."""
+        N, C, G, want_cls, pk = t.N, self.C, t.G, t.want_cls, t.packs[0] if t.packs is not None else None
+        b = t.bn[j] if t.bn is not None else None
+        nchw, cls, stats = t.out["nchw"][j], t.out["cls"][j], t.out["stats"]
+        if t.carry:
+            t.x_bn[:t.carry * N].copy_(t.store[j, :t.carry * N])
+        if t.tail:
+            t.store[j, :t.tail * N].copy_(t.ws["x"][(t.Bt - t.tail) * N:t.Bt * N])
+        # ONE call for all batches of the group: statistics, normalisation and outputs per batch (mvp_bn_tokens_args.groups)
+        ops.bn_tokens_to_nchw(
+            t.x_bn, t.B, N, C, t.hw, workspace=t.bn_ws, stats=stats[0, j],
+            gamma=b["weight"] if b else None, beta=b["bias"] if b else None,
+            running_mean=b["running_mean"] if b else None, running_var=b["running_var"] if b else None,
+            nchw=nchw[0], tok=pk.tok if pk else None, ld_tok=pk.Cpad if pk else 0, col_off=j * C,
+            mode=t.bn_mode, cls_out=cls[0] if want_cls else None, num_batches_tracked=b.get("num_batches_tracked") if b else None, defer_running=t.defer,
+            groups=G, stats_gstride=stats.stride(0), nchw_gstride=nchw.stride(0),
+            tok_gstride=(pk.Mpad * pk.Cpad) if pk else 0, cls_gstride=cls.stride(0) if want_cls else 0)
         for g in range(G):
-            if running[g]:  # all taps of a batch in ONE launch on the consumer's stream (mvp_bn_running_update_n; the modules are distinct)
-                pipeline.defer(lambda items=running[g]: ops.bn_running_update_many(items), group=g)
-            outs_g[g].stats = out["stats"][g]
-            if packed_g[g] is not None:
-                outs_g[g].packed = packed_g[g]
-                register_pack(outs_g[g], packed_g[g])
-        return outs_g[0] if (G == 1 and span is None) else TapGroups(outs_g)
+            if want_cls:
+                t.outs[g].cls.append(cls[g])
+            if t.defer and b is not None and b.get("running_mean") is not None:
+                t.running[g].append((stats[g, j], b["running_mean"], b["running_var"], b.get("num_batches_tracked"), C))
+            t.outs[g].append(nchw[g])
 
     def last_block_qkv(self, images: torch.Tensor) -> torch.Tensor:
         """The fused qkv projection of the LAST block (fp32 [B, N, 3C]: q | k | v, heads side by side) — what the reference captures
@@ -527,13 +508,9 @@ class ViTEngine:
         N = self.n_prefix + gh * gw
         for i in range(self.depth - 1):
             self.run_block(i, ws, B, N)
-        blk, C, M = self.blocks[self.depth - 1], self.C, B * N
-        f2 = self.f16x2
-        ops.layernorm(ws["x"], blk["n1w"], blk["n1b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
-        out = torch.empty(M, 3 * C, dtype=torch.float32, device=self.device)
-        ops.gemm(ws["xn"], blk["qkv_w"], M, 3 * C, C, bias=blk["qkv_b"], out_f32=out, precision=lib.PREC_F16X2 if f2 else self.precision,
-                 w_ilv=blk.get("qkv_w_ilv"))
-        return out.view(B, N, 3 * C)
+        out = torch.empty(B * N, 3 * self.C, dtype=torch.float32, device=self.device)
+        self._ln1_qkv(self.depth - 1, ws, B * N, out_f32=out)
+        return out.view(B, N, 3 * self.C)
 
     def forward_tokens(self, images: torch.Tensor, n_blocks: Optional[int] = None) -> torch.Tensor:
         """Raw fp32 token stream after ``n_blocks`` blocks ([B, N, C]); for tests / CLS outputs."""
