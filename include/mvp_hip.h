@@ -74,6 +74,7 @@ typedef struct {
                                 the tile kernels on every shape measured), so splitk < 0 is now MVP_EINVAL.  Added: mvp_gemm_route
                                 (and its struct mvp_gemm_route_t, tagged like the later additions within 7), which reports the kernel
                                 mvp_gemm_bias_act_res would run.  Every other struct, mvp_gemm_args included, as in 7.
+                                Added within 8: mvp_rope2d_qkv (a new export with its own tagged argument struct; no existing struct changed).
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -293,6 +294,39 @@ typedef struct {
                                   pair of MVP_PREC_F16X2 (mvp_gemm_args.out_f16_col0 = -(first column of the V third)): Q.K^T as two f16 products instead of
                                   three bf16 ones, same ~2^-18 relative error per term; Q and K must stay within fp16's range (saturating) */
 int mvp_attention_fwd(const mvp_attention_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)
+ * 2-D rotary position embedding of the fused qkv projection: CroCo v2's RoPE100, the reference's RoPE2D.forward
+ * (evals/models/croco_models/pos_embed.py:110-157) applied to q and k in Attention.forward (croco_models/blocks.py:94-103).
+ * Sits between the qkv GEMM and mvp_attention_fwd: reads the projection as fp32 [M, ld_in] (the GEMM's out_f32 form), rotates the Q and K
+ * thirds, passes V through, and writes the pair buffer mvp_attention_fwd reads — every third in exactly the 16-bit form the qkv GEMM's
+ * epilogue writes for the same (precision, v_format) (mvp_gemm_args.out_f16_col0 = 0 / 2*H*64 / -2*H*64 for v_format 0 / 1 / 2;
+ * one definition of each form, shared with the epilogues: <= 2^-17 relative each).
+ * Per head, dims 0..31 take the token's y coordinate and dims 32..63 its x coordinate; within a 32-wide half, with
+ * c = cos_tab[pos][d], s = sin_tab[pos][d]:
+ *     d <  16:  out[d] = t[d] * c - t[d + 16] * s
+ *     d >= 16:  out[d] = t[d] * c + t[d - 16] * s
+ * in fp32 as SEPARATE multiplies and one add / subtract (never contracted into an fma): torch's (t * cos) + (rotate_half(t) * sin),
+ * bit for bit.  Positions come from the row index alone: token t = m % N; t < n_prefix is not rotated; else p = t - n_prefix,
+ * y = p / gw, x = p % gw.  Stateless, no workspace, no sync.
+ * MVP_EINVAL: NULL pointers (out_lo may be NULL under MVP_PREC_BF16 only, and is then not written), M % N != 0,
+ * N != n_prefix + gh * gw, tab_rows < max(gh, gw), ld_in or ld_out < 3 * H * 64, rows not 16-byte aligned (pointers % 16, ld_in % 4,
+ * ld_out % 8), a precision other than MVP_PREC_BF16 / MVP_PREC_BF16X3, a v_format other than 0 under a precision other than MVP_PREC_BF16X3,
+ * M * 24 * H >= 2^31 (one thread per 8 values, indexed in 32 bits).
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_rope2d_qkv_args mvp_rope2d_qkv_args;
+struct mvp_rope2d_qkv_args {
+  const float* qkv;            /* [M, ld_in] fp32, col = which*H*64 + head*64 + d                   */
+  mvp_bf16* out_hi; mvp_bf16* out_lo;  /* [M, ld_out] pair, MVP_PAIR_SEPARATE                       */
+  const float* cos_tab; const float* sin_tab;  /* [tab_rows, 32] fp32, row = grid coordinate        */
+  int M, N, H;                 /* rows, tokens per image, heads; M % N == 0                         */
+  int n_prefix, gh, gw;        /* N == n_prefix + gh*gw                                             */
+  int tab_rows;                /* >= max(gh, gw), checked on the host                               */
+  int ld_in, ld_out;
+  int precision, v_format;     /* as mvp_attention_args: which 16-bit form each third gets          */
+};
+int mvp_rope2d_qkv(const mvp_rope2d_qkv_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * CLS row writer: x[b, 0, :] = cls[:] + pos[0, :]   (ibot_transformers.py:347-352).

@@ -2,6 +2,8 @@
 no longer exist and raises ImportError; hydra only needs the sub-modules to be importable)."""
 from . import probes  # noqa: F401
 from .clip import CLIP  # noqa: F401
+from .croco import CROCO  # noqa: F401
+from .crocov2 import CROCOV2  # noqa: F401
 from .dino import DINO  # noqa: F401
 from .ibot import iBOT  # noqa: F401
 from .mae import MAE  # noqa: F401

@@ -354,6 +354,89 @@ def siglip_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return timm_siglip_to_engine(sd)
 
 
+# ---------------------------------------------------------------- CroCo / CroCo v2 (cross-view completion; plain ViT-B/16 encoders without a class token)
+CROCO_CKPT_FILES = {"croco": "CroCo.pth", "crocov2": "CroCo_V2_ViTBase_BaseDecoder.pth"}  # the published files, looked for under MVP_CKPT_DIR
+_CROCO_DROPPED = ("enc_norm.", "mask_token", "decoder_embed.", "dec_", "prediction_head.")  # never on the tap path (croco.py:150-178)
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def croco_model_dict(sd: Dict) -> Dict[str, torch.Tensor]:
+    """The model's tensors out of the published layout ``{"model": ..., "croco_kwargs": ...}``, or the bare dict itself."""
+    return sd["model"] if isinstance(sd.get("model"), dict) else sd
+
+
+def croco_to_engine(sd: Dict) -> Dict[str, torch.Tensor]:
+    """A CroCo / CroCo v2 checkpoint (the published ``{"model": ..., "croco_kwargs": ...}``, or the bare model dict; a dict already in
+    the engine's layout passes through) -> the keys the engine reads: ``enc_blocks.i.*`` -> ``blocks.i.*``, ``patch_embed.proj.*`` kept,
+    ``enc_pos_embed`` [n, C] -> ``pos_embed`` [1, n, C] (CroCo v1: the fixed sin-cos table without a CLS entry; RoPE models have none).
+    Dropped: ``enc_norm.*`` (the final norm is never applied on the tap path), ``mask_token``, ``decoder_embed.*``, ``dec_*`` and
+    ``prediction_head.*`` (the decoder)."""
+    m = croco_model_dict(sd)
+    if not any(k.startswith("enc_blocks.") for k in m):
+        return dict(m)
+    out = {}
+    for k, v in m.items():
+        if k.startswith(_CROCO_DROPPED):
+            continue
+        if k.startswith("enc_blocks."):
+            out["blocks." + k[len("enc_blocks."):]] = v
+        elif k == "enc_pos_embed":
+            out["pos_embed"] = v.unsqueeze(0)
+        elif k.startswith("patch_embed.proj."):
+            out[k] = v
+        else:
+            raise KeyError(f"croco_to_engine: unexpected key {k!r}")
+    return out
+
+
+def engine_to_croco(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of croco_to_engine on the encoder's keys (no ``enc_norm`` / decoder)."""
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("blocks."):
+            out["enc_blocks." + k[len("blocks."):]] = v
+        elif k == "pos_embed":
+            out["enc_pos_embed"] = v[0]
+        else:
+            out[k] = v
+    return out
+
+
+def random_croco_state_dict(embed_dim=768, depth=12, patch=16, img=224, pos_embed="cosine", seed=0, in_chans=3, dec_dim=None) -> Dict:
+    """Seeded random CroCo weights in the published layout ``{"model": ..., "croco_kwargs": ...}`` (used when no local checkpoint exists).
+    ``img``: the model's image size, an int or (height, width); ``pos_embed``: 'cosine' (CroCo v1: ``enc_pos_embed`` is the sin-cos table
+    of ``get_2d_sincos_pos_embed(C, grid, 0)``, croco_models/pos_embed.py:22-69) or 'RoPE<freq>' (CroCo v2: no table).  Blocks with
+    non-trivial LayerNorm affines and biases and Q / K projections large enough for peaked attention (with trunc-normal 0.02 weights the
+    softmax is near uniform and a wrong position form moves the features by less than the 1e-3 feature contract), plus ``enc_norm``, ``mask_token`` and a few decoder tensors (loaded, unused here)."""
+    g = torch.Generator().manual_seed(seed)
+    ih, iw = _pair(img)
+    grid = (ih // patch, iw // patch)
+    dec = dec_dim or (512 if embed_dim == 768 else embed_dim // 2)
+    kw = dict(img_size=(ih, iw) if ih != iw else ih, patch_size=patch, enc_embed_dim=embed_dim, enc_depth=depth, enc_num_heads=embed_dim // 64,
+              dec_embed_dim=dec, dec_depth=1, dec_num_heads=max(1, dec // 64), pos_embed=pos_embed)
+    m = {}
+    bound = math.sqrt(6.0 / (in_chans * patch * patch + embed_dim))  # (xavier-uniform on the flattened patch weight, as MAE / CroCo)
+    m["patch_embed.proj.weight"] = (torch.rand(embed_dim, in_chans, patch, patch, generator=g) * 2 - 1) * bound
+    m["patch_embed.proj.bias"] = 0.02 * torch.randn(embed_dim, generator=g)
+    if pos_embed == "cosine":
+        m["enc_pos_embed"] = torch.from_numpy(sincos_pos_embed_2d(embed_dim, grid, add_cls_token=False)).float()
+        m["dec_pos_embed"] = torch.from_numpy(sincos_pos_embed_2d(dec, grid, add_cls_token=False)).float()
+    elif not pos_embed.startswith("RoPE"):
+        raise NotImplementedError("Unknown pos_embed " + pos_embed)
+    _random_blocks(m, "enc_blocks.", _TIMM_BLOCK, embed_dim, depth, g)
+    for i in range(depth):  # Q and K rows at std 1.5 / sqrt(C): logits of a few units, attention peaked enough for the positions to matter
+        m[f"enc_blocks.{i}.attn.qkv.weight"][:2 * embed_dim] *= 1.5 / (0.02 * math.sqrt(embed_dim))
+    m["enc_norm.weight"], m["enc_norm.bias"] = torch.ones(embed_dim), torch.zeros(embed_dim)
+    m["mask_token"] = torch.zeros(1, 1, dec)
+    m["decoder_embed.weight"], m["decoder_embed.bias"] = 0.02 * torch.randn(dec, embed_dim, generator=g), torch.zeros(dec)
+    m["dec_norm.weight"], m["dec_norm.bias"] = torch.ones(dec), torch.zeros(dec)
+    m["prediction_head.weight"], m["prediction_head.bias"] = 0.02 * torch.randn(patch * patch * 3, dec, generator=g), torch.zeros(patch * patch * 3)
+    return {"model": m, "croco_kwargs": kw}
+
+
 def sincos_pos_embed_2d(embed_dim: int, grid_hw, add_cls_token: bool = True) -> np.ndarray:
     """evals/models/utils.py:75-102 + HF get_2d_sincos_pos_embed_from_grid (MAE): half of the
     channels encode the w coordinate ("w goes first"), half the h coordinate; each half is
@@ -393,7 +476,7 @@ class ViTParams(nn.Module):
                     setattr(mod, p, _Named())
                 mod = getattr(mod, p)
             mod.register_parameter(parts[-1], nn.Parameter(v.clone().float(), requires_grad=False))
-        self.embed_dim = sd["cls_token" if "cls_token" in sd else "pos_embed"].shape[-1]
+        self.embed_dim = (sd["cls_token"] if "cls_token" in sd else sd["pos_embed"]).shape[-1] if ("cls_token" in sd or "pos_embed" in sd) else sd["patch_embed.proj.weight"].shape[0]
         self.depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
 
     @property
@@ -415,6 +498,7 @@ class ViTBackbone(nn.Module):
     pos_embed_mode = "dino"
     tap_input_of_block = False
     act = "gelu"  # after fc1: 'gelu' (erf), 'quick_gelu', 'gelu_tanh' (ViTEngine)
+    rope_freq = None  # CroCo v2: RoPE<freq> on Q and K of every block (ViTEngine(rope_freq=...)); None: no rotation
     supports_pipelining = True  # per-slot buffers, tap-BN running-statistics updates deferred to the consumer (mvp/pipeline.py)
     graph_safe = True  # a pipelined forward launches only this library's kernels on fixed buffers: it can be captured in a hipGraph
 
@@ -440,7 +524,7 @@ class ViTBackbone(nn.Module):
         return getattr(self, self.params_attr)
 
     def _signature(self):
-        return tuple((p.data_ptr(), p._version) for p in self._params().parameters()) + (self._precision, self.act)
+        return tuple((p.data_ptr(), p._version) for p in self._params().parameters()) + (self._precision, self.act, self.rope_freq)
 
     def engine(self) -> ViTEngine:
         sig = self._signature()
@@ -451,7 +535,7 @@ class ViTBackbone(nn.Module):
                 raise lib.MvpError("backbone parameters are on the CPU: call model.to('cuda') — the HIP path has no CPU fallback")
             sd = {k: v for k, v in params.state_dict().items()}
             self._engine_obj = ViTEngine(sd, heads=self.heads, patch=self.patch_size, ln_eps=self.ln_eps, precision=self._precision,
-                                         device=dev, pos_embed_mode=self.pos_embed_mode, act=self.act)
+                                         device=dev, pos_embed_mode=self.pos_embed_mode, act=self.act, rope_freq=self.rope_freq)
             self.n_prefix = self._engine_obj.n_prefix
             self._engine_sig = sig
         return self._engine_obj

@@ -91,6 +91,11 @@ class PrefixRowsArgs(C.Structure):  # mvp_prefix_rows_args: CLS + register rows 
     _fields_ = [("cls", _vp), ("pos0", _vp), ("reg", _vp), ("x", _vp), ("B", _i), ("N", _i), ("C", _i), ("R", _i)]
 
 
+class Rope2dQkvArgs(C.Structure):  # mvp_rope2d_qkv_args: 2-D RoPE between the qkv GEMM and attention (added within ABI 8)
+    _fields_ = [("qkv", _vp), ("out_hi", _vp), ("out_lo", _vp), ("cos_tab", _vp), ("sin_tab", _vp), ("M", _i), ("N", _i), ("H", _i),
+                ("n_prefix", _i), ("gh", _i), ("gw", _i), ("tab_rows", _i), ("ld_in", _i), ("ld_out", _i), ("precision", _i), ("v_format", _i)]
+
+
 class BnTokensArgs(C.Structure):
     _fields_ = [("x", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("stats", _vp),
                 ("nchw", _vp), ("tok_hi", _vp), ("tok_lo", _vp), ("ld_tok", _i), ("col_off", _i),
@@ -273,10 +278,13 @@ SYMBOLS = {
     "mvp_gemm_scaled": GemmScaledArgs,
     "mvp_patch_gather_ld": PatchGatherLdArgs,
     "mvp_prefix_rows": PrefixRowsArgs,
+    "mvp_rope2d_qkv": Rope2dQkvArgs,
 }
 
 # the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
 NEW_STRUCTS_ABI7 = {"mvp_gemm_scaled_args": GemmScaledArgs, "mvp_patch_gather_ld_args": PatchGatherLdArgs, "mvp_prefix_rows_args": PrefixRowsArgs}
+
+NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs}  # the same for the additions of / within ABI 8
 
 _lib: Optional[C.CDLL] = None
 

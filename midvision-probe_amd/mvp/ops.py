@@ -295,6 +295,26 @@ def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precis
     _traced("attention", "4x32q", precision, 4.0 * B * H * N * N * 64, lambda: lib.call("mvp_attention_fwd", a))
 
 
+def rope2d_qkv(qkv_f32: torch.Tensor, out: Pair, cos_tab: torch.Tensor, sin_tab: torch.Tensor, M: int, N: int, H: int, n_prefix: int,
+               gh: int, gw: int, precision: int, v_f16: bool = False, qk_f16: bool = False, ld_in=None, ld_out=None) -> None:
+    """2-D RoPE of the fused qkv projection (mvp_rope2d_qkv): ``qkv_f32`` [M, 3 * H * 64] fp32 (``gemm(..., out_f32=...)``) -> the pair
+    ``out`` that ``attention`` reads, Q and K rotated by each token's (y, x) grid position, V passed through, every third in the form
+    ``gemm(..., f16_col0=...)`` writes for the same ``v_f16`` / ``qk_f16`` (see ``attention``).  ``cos_tab`` / ``sin_tab``: fp32
+    [rows >= max(gh, gw), 32], row = grid coordinate."""
+    if qk_f16 and not v_f16:
+        raise lib.MvpError("rope2d_qkv: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
+    _chk(cos_tab, torch.float32, "rope2d_qkv.cos_tab")
+    _chk(sin_tab, torch.float32, "rope2d_qkv.sin_tab")
+    if qkv_f32.dtype != torch.float32 or cos_tab.dim() != 2 or cos_tab.shape[1] != 32 or sin_tab.shape != cos_tab.shape:
+        raise lib.MvpError("rope2d_qkv: fp32 projection and fp32 [rows, 32] cos / sin tables of one shape expected")
+    a = lib.Rope2dQkvArgs(lib.ptr(qkv_f32), lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(cos_tab), lib.ptr(sin_tab), M, N, H, n_prefix, gh, gw,
+                          int(cos_tab.shape[0]), ld_in if ld_in is not None else 3 * H * 64, ld_out if ld_out is not None else 3 * H * 64,
+                          precision, (2 if qk_f16 else 1) if v_f16 else 0)
+    # algorithmic HBM bytes: the fp32 projection read once, the 16-bit pair (or single bf16) written once
+    nb = M * 3 * H * 64 * (4 + (4 if out[1] is not None else 2))
+    _traced("hbm", "rope2d_qkv_kernel", 0, float(nb), lambda: lib.call("mvp_rope2d_qkv", a))
+
+
 def cls_rows(cls: torch.Tensor, pos0: torch.Tensor, x: torch.Tensor, B: int, N: int, Cdim: int) -> None:
     lib.call("mvp_cls_rows", lib.ClsRowsArgs(lib.ptr(cls), lib.ptr(pos0), lib.ptr(x), B, N, Cdim))
 

@@ -151,7 +151,8 @@ def plan_taps(Bt: int, groups) -> Tuple[int, int, int, int]:
 
 class ViTEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, heads: int, patch: int = 16, ln_eps: float = 1e-6,
-                 precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True, act: str = "gelu"):
+                 precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True, act: str = "gelu",
+                 rope_freq: Optional[float] = None):
         """``state_dict`` in the DINO / timm layout; DINOv2's extras are picked up from it: ``register_tokens`` [1, R, C] (then
         n_prefix = 1 + R) and ``blocks.i.ls1.gamma`` / ``blocks.i.ls2.gamma`` (LayerScale, fused into the proj / fc2 epilogues).
         So are CLIP's and SigLIP's: ``norm_pre.weight`` / ``norm_pre.bias`` (a LayerNorm over the residual stream before block 0, in place),
@@ -161,7 +162,10 @@ class ViTEngine:
         pos_embed_mode: 'dino' (bicubic with the +0.1 scale nudge), 'fixed', 'dinov2_reg' (bicubic to the grid size, antialiased:
         DINOv2's register models), or 'resize_aa' (the same resample, applied whenever the table's grid-entry COUNT differs from
         gh * gw — the reference's resize_pos_embed, evals/models/utils.py:12-52 — with or without a CLS entry).
-        act: the activation after fc1: 'gelu' (erf), 'quick_gelu' (x sigmoid(1.702 x): OpenAI CLIP) or 'gelu_tanh' (SigLIP)."""
+        act: the activation after fc1: 'gelu' (erf), 'quick_gelu' (x sigmoid(1.702 x): OpenAI CLIP) or 'gelu_tanh' (SigLIP).
+        rope_freq: CroCo v2's RoPE<freq> (100.0 for the published models): Q and K of every block are rotated by the token's (y, x) grid
+        position (mvp_rope2d_qkv, between the qkv GEMM — which then writes fp32 — and attention).  The state dict may then come without
+        ``pos_embed`` (C is read from the patch-embedding weight and ``tokens`` adds no position residual)."""
         self.device = torch.device(device)
         self.precision = parse_precision(precision)
         # 'f16x2': a bf16x3 engine (buffers, patch embedding, attention, taps) whose four block GEMMs run two products (lib.PREC_F16X2)
@@ -183,12 +187,15 @@ class ViTEngine:
         self.act_name, self.act = act, ACTIVATIONS[act]
         sd = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in state_dict.items()}
         self.has_cls = "cls_token" in sd
-        self.C = sd["cls_token" if self.has_cls else "pos_embed"].shape[-1]
+        self.rope_freq = None if rope_freq is None else float(rope_freq)
+        if "pos_embed" not in sd and (self.rope_freq is None or self.has_cls):
+            raise lib.MvpError("state dict without pos_embed: only a RoPE model without a class token has none (rope_freq=...)")
+        self.C = sd["cls_token"].shape[-1] if self.has_cls else sd["pos_embed"].shape[-1] if "pos_embed" in sd else sd["patch_embed.proj.weight"].shape[0]
         if self.C != heads * 64:
             raise lib.MvpError(f"attention kernel requires head_dim 64 (C={self.C}, heads={heads})")
         self.depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
         self.cls = sd["cls_token"].reshape(-1).contiguous() if self.has_cls else None
-        self.pos_embed = sd["pos_embed"]  # [1, 1+n, C] fp32 ([1, n, C] without a CLS token)
+        self.pos_embed = sd.get("pos_embed")  # [1, 1+n, C] fp32 ([1, n, C] without a CLS token); None: a RoPE model without a table
         reg = sd.get("register_tokens")
         self.reg = reg.reshape(-1, self.C).contiguous() if reg is not None and reg.numel() else None  # [R, C]
         if not self.has_cls and self.reg is not None:
@@ -230,6 +237,7 @@ class ViTEngine:
         self.hidden = self.blocks[0]["fc1_b"].numel()
         self._buffers = EngineBuffers()  # everything a forward reuses, per pipeline slot (mvp/buffers.py)
         self._pos: Dict[Tuple[int, int], torch.Tensor] = {}
+        self._rope: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}  # (gh, gw) -> cos / sin tables [max(gh, gw), 32] (rope_for)
         pipeline.publish()  # the split weights are read by forwards on any stream
 
     # ------------------------------------------------------------------ helpers
@@ -245,7 +253,10 @@ class ViTEngine:
             ilv = (pr == PREC_BF16X3 and os.environ.get("MVP_ILV", "1") != "0" and C % 32 == 0 and self.hidden % 32 == 0 and
                    all(ops.gemm_tile(M, n, k, gp, 1, pipeline.tile_policy()).startswith("pp ") for n, k in ((3 * C, C), (C, C), (self.hidden, C), (C, self.hidden))))
             xfull = torch.empty(M + headroom * N, C, dtype=torch.float32, device=dev)
+            # RoPE engines only: the fp32 projection that mvp_rope2d_qkv reads, and the grid its positions come from
+            rope = dict(qkv_f32=torch.empty(M, 3 * C, dtype=torch.float32, device=dev), grid=(gh, gw)) if self.rope_freq is not None else {}
             return dict(
+                **rope,
                 xfull=xfull, headroom=headroom, x=xfull[headroom * N:],
                 xn=ops.IlvPair(M, C, dev) if ilv else ops.empty_pair((M, C), pr, dev),
                 qkv=ops.empty_pair((M, 3 * C), pr, dev),
@@ -261,7 +272,24 @@ class ViTEngine:
         maps), the carry stores and the position tables.  A captured hipGraph of that slot's forward holds their raw addresses: the
         pipeline keeps this list alive with the graph, because the engine itself drops the buffers of other resolutions when a new one
         arrives."""
-        return self._buffers.snapshot(slot) + list(self._pos.values())
+        return self._buffers.snapshot(slot) + list(self._pos.values()) + [t for cs in self._rope.values() for t in cs]
+
+    def rope_for(self, gh: int, gw: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The cos / sin tables of RoPE<rope_freq> for a gh x gw grid, fp32 [max(gh, gw), 32], row = grid coordinate: the reference's
+        RoPE2D.get_cos_sin (croco_models/pos_embed.py:119-129) with D = 32 (half a head) and seq_len = the largest coordinate + 1,
+        evaluated in fp32 ON THE CPU with the same torch expressions and then copied — bit-equal to the reference's CPU tables.  Cached
+        per grid beside the position tables."""
+        key = (gh, gw)
+        cs = self._rope.get(key)
+        if cs is None:
+            D = 32
+            inv_freq = 1.0 / (self.rope_freq ** (torch.arange(0, D, 2).float() / D))
+            t = torch.arange(max(gh, gw), dtype=inv_freq.dtype)
+            freqs = torch.einsum("i,j->ij", t, inv_freq)
+            freqs = torch.cat((freqs, freqs), dim=-1)
+            cs = self._rope[key] = (freqs.cos().contiguous().to(self.device), freqs.sin().contiguous().to(self.device))
+            pipeline.publish()
+        return cs
 
     def pos_for(self, gh: int, gw: int, dim2: int, dim3: int) -> torch.Tensor:
         """Pos-embed for a gh x gw grid.  'dino': bicubic resize with the +0.1 scale nudge of
@@ -323,10 +351,12 @@ class ViTEngine:
             ops.patch_gather(images, ws["patches"], P, gh, gw, ph // 2, pw // 2)
         else:
             ops.patch_gather_ld(images, ws["patches"], P, gh, gw, ph // 2, pw // 2, Kp)
-        pos = self.pos_for(gh, gw, H + ph, W + pw)
+        pos = self.pos_for(gh, gw, H + ph, W + pw) if self.pos_embed is not None else None  # (None: RoPE, nothing to add here)
         # x[b, npre+p, :] = patches · Wᵀ + bias + pos[1+p]   (row remap skips the CLS / register slots)
         ops.gemm(ws["patches"], self.w_patch, B * gh * gw, C, Kp, bias=self.b_patch, residual=pos[1:] if self.has_cls else pos, out_f32=ws["x"],
-                 precision=self.precision, row_group=gh * gw, row_group_stride=N, row_group_off=npre, res_row_mod=gh * gw)
+                 precision=self.precision, row_group=gh * gw, row_group_stride=N, row_group_off=npre, res_row_mod=gh * gw if pos is not None else 0)
+        if self.rope_freq is not None:
+            self.rope_for(gh, gw)  # (built and published here, before any block runs)
         if not self.has_cls:
             pass  # no prefix rows at all (SigLIP)
         elif self.reg is None:
@@ -365,7 +395,13 @@ class ViTEngine:
         gp = lib.PREC_F16X2 if f2 else pr  # precision of the four block GEMMs
         x = ws["x"]
         vf16, qk16 = self.att_v_f16, self.att_qk_f16
-        self._ln1_qkv(i, ws, M)
+        if self.rope_freq is None:
+            self._ln1_qkv(i, ws, M)
+        else:  # the projection as fp32, then rotation + conversion into the forms the attention kernel reads (mvp_rope2d_qkv)
+            gh, gw = ws["grid"]
+            cos, sin = self.rope_for(gh, gw)
+            self._ln1_qkv(i, ws, M, out_f32=ws["qkv_f32"])
+            ops.rope2d_qkv(ws["qkv_f32"], ws["qkv"], cos, sin, M, N, self.heads, self.n_prefix, gh, gw, pr, v_f16=vf16, qk_f16=qk16)
         if chk:  # (after the projection: ws["xn"] still holds LayerNorm 1's output)
             self._check_f16_range(f"block {i}: LayerNorm 1 output", ws["xn"], M)
         if chk and qk16:

@@ -24,7 +24,9 @@ sys.path[:0] = [REPO, os.path.join(REPO, "midvision-probe_amd")]
 import torch  # noqa: E402
 
 MODELS = {"dino_b16": ("dino", "vitb16", "dense"), "dinov2_b14": ("dinov2", "vitb14", "dense-cls"),
-          "dinov2_b14_reg": ("dinov2", "vitb14_reg", "dense-cls"), "dinov2_l14": ("dinov2", "vitl14", "dense-cls")}
+          "dinov2_b14_reg": ("dinov2", "vitb14_reg", "dense-cls"), "dinov2_l14": ("dinov2", "vitl14", "dense-cls"),
+          # the same GEMMs; crocov2 adds mvp_rope2d_qkv and the fp32 qkv output per block
+          "croco_b16": ("croco", "vitb16", "dense"), "crocov2_b16": ("crocov2", "vitb16", "dense")}
 
 
 def build(name, precision, dev):
@@ -36,7 +38,13 @@ def build(name, precision, dev):
     dn, mn, out = MODELS[name]
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")  # seeded random init
-        model = DINO(dino_name=dn, model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
+        if dn in ("croco", "crocov2"):
+            from evals.models.croco import CROCO
+            from evals.models.crocov2 import CROCOV2
+
+            model = (CROCO if dn == "croco" else CROCOV2)(model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
+        else:
+            model = DINO(dino_name=dn, model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
     torch.manual_seed(0)
     probe = DepthHead(feat_dim=model.feat_dim, head_type="linear", kernel_size=1, prediction_type="bindepth", min_depth=0.001, max_depth=10).to(dev)
     opt = FlatAdamW([{"params": probe.parameters(), "lr": 5e-4}])
