@@ -75,6 +75,8 @@ typedef struct {
                                 (and its struct mvp_gemm_route_t, tagged like the later additions within 7), which reports the kernel
                                 mvp_gemm_bias_act_res would run.  Every other struct, mvp_gemm_args included, as in 7.
                                 Added within 8: mvp_rope2d_qkv (a new export with its own tagged argument struct; no existing struct changed).
+                                Added within 8: mvp_attention_bias_fwd (attention with a dense per-head additive logit bias; a new export with its own
+                                tagged argument struct that wraps mvp_attention_args unchanged).
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -294,6 +296,26 @@ typedef struct {
                                   pair of MVP_PREC_F16X2 (mvp_gemm_args.out_f16_col0 = -(first column of the V third)): Q.K^T as two f16 products instead of
                                   three bf16 ones, same ~2^-18 relative error per term; Q and K must stay within fp16's range (saturating) */
 int mvp_attention_fwd(const mvp_attention_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)
+ * Attention with a dense per-head additive bias on the logits (BEiT's relative-position bias; the base of SAM's):
+ *   O = softmax(Q K^T * att.scale + bias[h]) V
+ * Everything else as mvp_attention_fwd (same kernels, same operand forms, same N <= 256 resident / streaming split).
+ * bias is fp32 [H][N][ld_bias], bias[h][q][k], the same for every image of the batch, in natural-log units, finite, of any sign and
+ * magnitude.  Columns k >= N of a row (up to 64 * ceil(N / 64)) may be read; they may hold anything, NaN included, and never reach
+ * the output.  No row q >= N and no head >= H is read.
+ * MVP_EINVAL: everything mvp_attention_fwd rejects; bias NULL or not 16-byte aligned; ld_bias % 4 != 0 or
+ * ld_bias < 64 * ceil(N / 64); bias_head_stride < N * ld_bias or bias_head_stride % 4 != 0 (every row starts 16-byte aligned).
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_attention_bias_args mvp_attention_bias_args;
+struct mvp_attention_bias_args {
+  mvp_attention_args att;      /* everything as mvp_attention_fwd */
+  const float* bias;           /* fp32 [H][N][ld_bias]: bias[h][q][k], the same for every image of the batch */
+  int64_t bias_head_stride;    /* elements; >= N * ld_bias, % 4 == 0 */
+  int ld_bias;                 /* elements; % 4 == 0 and >= 64 * ceil(N / 64) */
+};
+int mvp_attention_bias_fwd(const mvp_attention_bias_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)

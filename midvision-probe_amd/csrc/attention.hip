@@ -36,6 +36,10 @@
 // — two products instead of three, one conversion per product instead of the split.  (lo stays bf16: an fp16 lo of a small v would
 // be a denormal.)  The running maximum is then only an exponent offset, so it is moved — and O, l rescaled — only when a row's
 // maximum rises by more than 2^6 above it (always at a pair's first tile): probabilities stay below 2^6 = 64, far inside fp16.
+// BIAS (mvp_attention_bias_fwd; BEiT's relative-position bias): both kernels and the tile routine take a ``bool BIAS`` template parameter;
+// a BIAS kernel's argument is mvp_attention_bias_args (mvp_attention_args + a dense fp32 [H][N][ld] logit bias).  Every bias path is under
+// ``if constexpr``, so the BIAS = false instantiations are the kernels of mvp_attention_fwd, instruction for instruction
+// (profiles/attention_bias_kernel_resources.txt).  See AttnBias below.
 #include "mvp_common.h"
 
 #ifndef MVP_ATT_NT
@@ -79,8 +83,22 @@ struct AttnState {
 // body is kept lean: raw v_exp_f32 (__builtin_amdgcn_exp2f: no denormal range fix-up, 5 instructions fewer per
 // element; probabilities below 2^-126 are zero either way) and the key-validity mask compiled only into the LAST
 // tile's instantiation.
-template <int SPLIT, bool LAST, int VF16 = 0>
-__device__ __forceinline__ void attn_tile(AttnState<SPLIT>& st, const char* kb, const char* vb, int key0, int N, float cs, int lane) {
+//
+// BIAS (mvp_attention_bias_fwd): softmax(Q K^T * scale + bias[h]).  The S accumulator of a lane holds 4 consecutive keys
+// (key0 + t*16 + g*4 + j) of one query, so the bias of one s[t][qt] is ONE 16-byte load from row q of head h (ab.row[qt] points at
+// bias[h][q][g*4]); the 8 loads of a tile are issued first, so they are in flight under the Q.K^T MFMA cluster.  After the cluster
+// s <- s * scale + bias (one fma per score, natural-log units) and ``cs`` is then log2(e) alone: key mask, tile maximum, the deferral
+// test of the VF16 forms, exp2 and the row sum all act on the biased value, through the very code of the unbiased kernels.
+// Padding columns (k >= N, may hold NaN) fall to the key mask, which selects; all-padding sub-tiles are not loaded at all.
+// The diagnostic knobs apply as they stand (MVP_ATT_ABLATE 1 / 3 drop the softmax / the Q.K^T products, not the bias load and fma).
+struct AttnBias {
+  const float* row[2];  // per qt: bias + h * head_stride + min(q, N - 1) * ld_bias + g * 4
+  float scale;
+};
+
+template <int SPLIT, bool LAST, int VF16 = 0, bool BIAS = false>
+__device__ __forceinline__ void attn_tile(AttnState<SPLIT>& st, const char* kb, const char* vb, int key0, int N, float cs, int lane,
+                                          const AttnBias& ab = AttnBias{}) {
   static_assert(!VF16 || SPLIT == 3, "the fp16-probability form belongs to the bf16x3 mode");
   const int g = lane >> 4, c16 = lane & 15;
   // LAST tile: only the first nsub 16-key sub-tiles hold real keys (N = 197: 5 keys of the 4th tile -> nsub = 1); the
@@ -91,6 +109,14 @@ __device__ __forceinline__ void attn_tile(AttnState<SPLIT>& st, const char* kb, 
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) s[t][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  f32x4_t bv[4][2];
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+        bv[t][qt] = (LAST && t >= nsub) ? f32x4_t{0.f, 0.f, 0.f, 0.f} : *(const f32x4_t*)(ab.row[qt] + key0 + t * 16);
+  }
   ATT_PRIO(1);
 #pragma unroll
   for (int ks = 0; ks < (MVP_ATT_ABLATE == 3 ? 0 : 2); ++ks) {
@@ -127,6 +153,14 @@ __device__ __forceinline__ void attn_tile(AttnState<SPLIT>& st, const char* kb, 
     }
   }
   ATT_PRIO(0);
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[t][qt][j] = __builtin_fmaf(s[t][qt][j], ab.scale, bv[t][qt][j]);
+  }
   // ---------------- online softmax (q on the lane; keys on registers + lane groups)
   const int kbase = key0 + g * 4;
   bf16x8_t p_hi[2][2], p_lo[2][2];  // VF16: p_lo = bf16(p) (the partner of v_lo), p_h = fp16(p)
@@ -325,8 +359,23 @@ __device__ __forceinline__ void attn_stage_piece(const mvp_attention_args& p, si
   }
 }
 
-template <int SPLIT, int VF16 = 0>
-__global__ __launch_bounds__(256) void attention_stream_kernel(const mvp_attention_args p) {
+// Kernel argument of the two kernels: the plain struct, or (BIAS) the struct that wraps it (its first member).
+template <bool BIAS> struct AttnKArgs { typedef mvp_attention_args type; };
+template <> struct AttnKArgs<true> { typedef mvp_attention_bias_args type; };
+__host__ __device__ __forceinline__ const mvp_attention_args& att_of(const mvp_attention_args& a) { return a; }
+__host__ __device__ __forceinline__ const mvp_attention_args& att_of(const mvp_attention_bias_args& a) { return a.att; }
+// The bias row pointers of this lane's two query rows (clamped like the Q load: no row >= N, no head >= H is read).
+__device__ __forceinline__ void attn_bias_rows(AttnBias& ab, const mvp_attention_bias_args& a, int h, int q0, int lane) {
+  const int g = lane >> 4, c16 = lane & 15;
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt)
+    ab.row[qt] = a.bias + (size_t)h * (size_t)a.bias_head_stride + (size_t)min(q0 + qt * 16 + c16, a.att.N - 1) * (size_t)a.ld_bias + g * 4;
+}
+__device__ __forceinline__ void attn_bias_rows(AttnBias&, const mvp_attention_args&, int, int, int) {}
+
+template <int SPLIT, int VF16 = 0, bool BIAS = false>
+__global__ __launch_bounds__(256) void attention_stream_kernel(const typename AttnKArgs<BIAS>::type pa) {
+  const mvp_attention_args& p = att_of(pa);
   f16_saturate_mode();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NARR = (SPLIT == 3) ? 2 : 1;
@@ -338,8 +387,13 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const mvp_attenti
   const size_t rowbase = (size_t)b * p.N;
   AttnState<SPLIT> st;
   attn_load_q<SPLIT>(st, p, rowbase, q0, h, lane);
-  const float cs = p.scale * 1.44269504088896340736f;  // softmax(x*scale) via exp2
+  const float cs = BIAS ? 1.44269504088896340736f : p.scale * 1.44269504088896340736f;  // softmax(x*scale) via exp2 (BIAS: the tile applies scale)
   const bool active = q0 < p.N;                         // wave-uniform
+  AttnBias ab{};
+  if constexpr (BIAS) {
+    ab.scale = p.scale;
+    if (active) attn_bias_rows(ab, pa, h, q0, lane);
+  }
 
   auto stage = [&](int buf, int kt) {
     char* base = smem + buf * STAGE;
@@ -353,8 +407,8 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const mvp_attenti
     if (kt + 1 < nkt) stage((kt + 1) & 1, kt + 1);
     if (active) {
       const char* kb = smem + (kt & 1) * STAGE;
-      if (kt == nkt - 1) attn_tile<SPLIT, true, VF16>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane);
-      else attn_tile<SPLIT, false, VF16>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane);
+      if (kt == nkt - 1) attn_tile<SPLIT, true, VF16, BIAS>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane, ab);
+      else attn_tile<SPLIT, false, VF16, BIAS>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane, ab);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -373,8 +427,10 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const mvp_attenti
 //   i+1's slot 0, and pair i+1's tiles t >= 1 fall into slots pair i has finished with when the pair-boundary barrier is passed.
 // Per pair: [tile 0 resident, Q in registers] -> issue tiles 1.. (land under tile 0's compute) -> tile 0 -> vmcnt(0) + barrier ->
 // issue next pair's tile 0 + Q -> tiles 1.. -> vmcnt(0) (the prefetch, issued long before) -> output stores -> barrier.
-template <int SPLIT, int VF16 = 0>
-__global__ __launch_bounds__(512) void attention_resident_kernel(const mvp_attention_args p) {
+// BIAS: the bias rows follow the pair the ring is on (h = bh % H of THIS iteration), like rowbase.
+template <int SPLIT, int VF16 = 0, bool BIAS = false>
+__global__ __launch_bounds__(512) void attention_resident_kernel(const typename AttnKArgs<BIAS>::type pa) {
+  const mvp_attention_args& p = att_of(pa);
   f16_saturate_mode();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NARR = (SPLIT == 3) ? 2 : 1;
@@ -383,9 +439,11 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const mvp_atten
   const int q0 = wave * 32;
   const int nkt = (p.N + 63) >> 6, nslot = nkt + 1;
   const int npair = p.B * p.H;
-  const float cs = p.scale * 1.44269504088896340736f;
+  const float cs = BIAS ? 1.44269504088896340736f : p.scale * 1.44269504088896340736f;
   const bool active = q0 < p.N;  // wave-uniform
   const int g = lane >> 4, c16 = lane & 15;
+  AttnBias ab{};
+  if constexpr (BIAS) ab.scale = p.scale;
 
   auto stage_tile = [&](int bh, int kt, int slot) {  // 8 waves x 8 rows = one 64-key tile
     const int b = bh / p.H, h = bh - b * p.H;
@@ -418,6 +476,9 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const mvp_atten
     const int b = bh / p.H, h = bh - b * p.H;
     const size_t rowbase = (size_t)b * p.N;
     const int s0 = (nkt * i) % nslot;  // slot of this pair's tile 0
+    if constexpr (BIAS) {
+      if (active) attn_bias_rows(ab, pa, h, q0, lane);
+    }
     // this pair's remaining tiles: their slots were released at the barrier that ended the previous pair
     for (int kt = 1; kt < nkt; ++kt) stage_tile(bh, kt, (s0 + kt) % nslot);
 #pragma unroll
@@ -435,8 +496,8 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const mvp_atten
     st.l_run[0] = st.l_run[1] = 0.f;
     if (active && MVP_ATT_ABLATE != 5) {
       const char* kb = smem + s0 * STAGE;
-      if (nkt == 1) attn_tile<SPLIT, true, VF16>(st, kb, kb + NARR * TILE, 0, p.N, cs, lane);
-      else attn_tile<SPLIT, false, VF16>(st, kb, kb + NARR * TILE, 0, p.N, cs, lane);
+      if (nkt == 1) attn_tile<SPLIT, true, VF16, BIAS>(st, kb, kb + NARR * TILE, 0, p.N, cs, lane, ab);
+      else attn_tile<SPLIT, false, VF16, BIAS>(st, kb, kb + NARR * TILE, 0, p.N, cs, lane, ab);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tiles 1.. landed (and the previous pair's stores have left)
     __syncthreads();
@@ -449,8 +510,8 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const mvp_atten
     if (active) {
       for (int kt = 1; kt < (MVP_ATT_ABLATE == 5 ? 0 : nkt); ++kt) {
         const char* kb = smem + ((s0 + kt) % nslot) * STAGE;
-        if (kt == nkt - 1) attn_tile<SPLIT, true, VF16>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane);
-        else attn_tile<SPLIT, false, VF16>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane);
+        if (kt == nkt - 1) attn_tile<SPLIT, true, VF16, BIAS>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane, ab);
+        else attn_tile<SPLIT, false, VF16, BIAS>(st, kb, kb + NARR * TILE, kt * 64, p.N, cs, lane, ab);
       }
     }
     // The prefetch was issued a whole pair's worth of tiles ago: this wait is free.  It comes BEFORE the output stores on purpose —
@@ -463,14 +524,15 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const mvp_atten
   }
 }
 
-template <int SPLIT, int VF16 = 0>
-int launch_attention(const mvp_attention_args* a, hipStream_t s) {
+template <int SPLIT, int VF16 = 0, bool BIAS = false>
+int launch_attention(const typename AttnKArgs<BIAS>::type* ka, hipStream_t s) {
+  const mvp_attention_args* a = &att_of(*ka);
   constexpr int NARR = (SPLIT == 3) ? 2 : 1;
   constexpr int STAGE = 2 * NARR * TILE;
   constexpr int SMEM_STREAM = 2 * STAGE, SMEM_RES = 5 * STAGE;  // resident kernel: ring of nkt + 1 <= 5 tile slots (160 KiB at bf16x3)
   static int configured = [] {
-    int e = (int)hipFuncSetAttribute((const void*)attention_stream_kernel<SPLIT, VF16>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_STREAM);
-    if (e == 0) e = (int)hipFuncSetAttribute((const void*)attention_resident_kernel<SPLIT, VF16>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_RES);
+    int e = (int)hipFuncSetAttribute((const void*)attention_stream_kernel<SPLIT, VF16, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_STREAM);
+    if (e == 0) e = (int)hipFuncSetAttribute((const void*)attention_resident_kernel<SPLIT, VF16, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_RES);
     return e;
   }();
   if (configured != 0) return MVP_ELAUNCH;
@@ -484,10 +546,10 @@ int launch_attention(const mvp_attention_args* a, hipStream_t s) {
     }();
     const int per_cu = (160 * 1024) / ((nkt + 1) * STAGE) > 0 ? (160 * 1024) / ((nkt + 1) * STAGE) : 1;
     const int grid = a->B * a->H < cus * per_cu ? a->B * a->H : cus * per_cu;
-    hipLaunchKernelGGL((attention_resident_kernel<SPLIT, VF16>), dim3(grid), dim3(512), (nkt + 1) * STAGE, s, *a);
+    hipLaunchKernelGGL((attention_resident_kernel<SPLIT, VF16, BIAS>), dim3(grid), dim3(512), (nkt + 1) * STAGE, s, *ka);
   } else {
     dim3 grid((a->N + 127) / 128, a->B * a->H);
-    hipLaunchKernelGGL((attention_stream_kernel<SPLIT, VF16>), grid, dim3(256), SMEM_STREAM, s, *a);
+    hipLaunchKernelGGL((attention_stream_kernel<SPLIT, VF16, BIAS>), grid, dim3(256), SMEM_STREAM, s, *ka);
   }
   MVP_LAUNCH_CHECK();
   return MVP_OK;
@@ -495,18 +557,42 @@ int launch_attention(const mvp_attention_args* a, hipStream_t s) {
 
 }  // namespace
 
-extern "C" int mvp_attention_fwd(const mvp_attention_args* a, void* stream) {
+// Host checks shared by the two exports; returns MVP_OK or MVP_EINVAL, launches nothing.
+static int attention_check(const mvp_attention_args* a) {
   if (!a || !a->qkv_hi || !a->out_hi) return MVP_EINVAL;
   if (a->B <= 0 || a->N <= 0 || a->H <= 0) return MVP_EINVAL;
   if ((a->ld_qkv & 7) || (a->ld_out & 3) || a->ld_qkv < 3 * a->H * 64 || a->ld_out < a->H * 64) return MVP_EINVAL;
   if (a->out_layout != MVP_PAIR_SEPARATE && (a->out_layout != MVP_PAIR_A_ILV32 || a->precision != MVP_PREC_BF16X3 || a->ld_out < 2 * a->H * 64)) return MVP_EINVAL;
   if (a->precision == MVP_PREC_BF16X3) {
     if (!a->qkv_lo || (!a->out_lo && a->out_layout == MVP_PAIR_SEPARATE)) return MVP_EINVAL;
-    if (a->v_format == MVP_ATT_V_F16) return launch_attention<3, 1>(a, (hipStream_t)stream);
-    if (a->v_format == MVP_ATT_V_F16_QK_F16) return launch_attention<3, 2>(a, (hipStream_t)stream);
-    if (a->v_format != MVP_ATT_V_BF16_PAIR) return MVP_EINVAL;
-    return launch_attention<3>(a, (hipStream_t)stream);
+    if (a->v_format != MVP_ATT_V_F16 && a->v_format != MVP_ATT_V_F16_QK_F16 && a->v_format != MVP_ATT_V_BF16_PAIR) return MVP_EINVAL;
+    return MVP_OK;
   }
   if (a->precision != MVP_PREC_BF16 || a->v_format != MVP_ATT_V_BF16_PAIR || a->out_f16) return MVP_EINVAL;
-  return launch_attention<1>(a, (hipStream_t)stream);
+  return MVP_OK;
+}
+
+template <bool BIAS>
+static int attention_dispatch(const typename AttnKArgs<BIAS>::type* ka, hipStream_t s) {
+  const mvp_attention_args* a = &att_of(*ka);
+  if (a->precision == MVP_PREC_BF16X3) {
+    if (a->v_format == MVP_ATT_V_F16) return launch_attention<3, 1, BIAS>(ka, s);
+    if (a->v_format == MVP_ATT_V_F16_QK_F16) return launch_attention<3, 2, BIAS>(ka, s);
+    return launch_attention<3, 0, BIAS>(ka, s);
+  }
+  return launch_attention<1, 0, BIAS>(ka, s);
+}
+
+extern "C" int mvp_attention_fwd(const mvp_attention_args* a, void* stream) {
+  if (attention_check(a) != MVP_OK) return MVP_EINVAL;
+  return attention_dispatch<false>(a, (hipStream_t)stream);
+}
+
+extern "C" int mvp_attention_bias_fwd(const mvp_attention_bias_args* a, void* stream) {
+  if (!a || attention_check(&a->att) != MVP_OK) return MVP_EINVAL;
+  if (!a->bias || ((uintptr_t)a->bias & 15)) return MVP_EINVAL;
+  const int64_t npad = 64 * (((int64_t)a->att.N + 63) / 64);
+  if ((a->ld_bias & 3) || a->ld_bias < npad) return MVP_EINVAL;
+  if (a->bias_head_stride < (int64_t)a->att.N * a->ld_bias || (a->bias_head_stride & 3)) return MVP_EINVAL;  // (every row 16-byte aligned)
+  return attention_dispatch<true>(a, (hipStream_t)stream);
 }

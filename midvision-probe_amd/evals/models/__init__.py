@@ -1,6 +1,7 @@
 """Working package init (the reference's evals/models/__init__.py:1-7 re-exports names that
 no longer exist and raises ImportError; hydra only needs the sub-modules to be importable)."""
 from . import probes  # noqa: F401
+from .beit_v2 import BEiTV2  # noqa: F401
 from .clip import CLIP  # noqa: F401
 from .croco import CROCO  # noqa: F401
 from .crocov2 import CROCOV2  # noqa: F401

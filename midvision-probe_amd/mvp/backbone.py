@@ -437,6 +437,100 @@ def random_croco_state_dict(embed_dim=768, depth=12, patch=16, img=224, pos_embe
     return {"model": m, "croco_kwargs": kw}
 
 
+# ---------------------------------------------------------------- BEiT v2 (ViT-B/16 with a per-block relative-position bias, no absolute position table)
+BEIT_CKPT_FILE = "beit_v2_vitb16.pth"  # the published file, looked for under MVP_CKPT_DIR
+_BEIT_SHARED_TABLE = "rel_pos_bias.relative_position_bias_table"
+
+
+def beit_grid(n_rows: int, grid=None):
+    """(gh, gw) a relative-position table of ``n_rows`` rows belongs to: ``grid`` when given (checked), else the square grid of that length."""
+    if grid is not None:
+        gh, gw = _pair(grid)
+    else:
+        gh = gw = (math.isqrt(max(n_rows - 3, 0)) + 1) // 2
+    if (2 * gh - 1) * (2 * gw - 1) + 3 != n_rows:
+        raise lib.MvpError(f"relative-position table of {n_rows} rows does not belong to a {gh} x {gw} grid ({(2 * gh - 1) * (2 * gw - 1) + 3} rows): "
+                           "re-interpolating tables to another grid (the reference's scipy path) is not supported")
+    return gh, gw
+
+
+def beit_to_engine(sd: Dict) -> Dict[str, torch.Tensor]:
+    """A BEiT v2 checkpoint (the published ``{"model": ...}``, or the bare dict; a dict already in the engine's layout passes through) ->
+    the keys the engine reads: ``attn.q_bias`` / ``attn.v_bias`` -> ``attn.qkv.bias`` = cat(q_bias, 0, v_bias) (the K bias is zero,
+    beit_model.py:152-162); ``gamma_1`` / ``gamma_2`` -> ``ls1.gamma`` / ``ls2.gamma``; ``attn.relative_position_bias_table`` ->
+    ``attn.rel_pos_bias_table``, a shared ``rel_pos_bias.relative_position_bias_table`` expanded to every block (beit_state_dict.py:14-28).
+    Dropped: every ``relative_position_index`` (recomputed), ``head.*`` and ``mask_token``."""
+    m = sd["model"] if isinstance(sd.get("model"), dict) else sd
+    if not any(k.endswith(("attn.q_bias", "gamma_1", "relative_position_bias_table")) for k in m):
+        return dict(m)
+    out = {}
+    shared = m.get(_BEIT_SHARED_TABLE)
+    for k, v in m.items():
+        if "relative_position_index" in k or k.startswith("head.") or k == "mask_token" or k == _BEIT_SHARED_TABLE:
+            continue
+        if k.endswith("attn.v_bias"):
+            continue
+        if k.endswith("attn.q_bias"):
+            p = k[:-len("q_bias")]
+            out[p + "qkv.bias"] = torch.cat((v, torch.zeros_like(v), m[p + "v_bias"]))
+        elif k.endswith(".gamma_1") or k.endswith(".gamma_2"):
+            out[k[:-len("gamma_1")] + ("ls1.gamma" if k.endswith("1") else "ls2.gamma")] = v
+        elif k.endswith("attn.relative_position_bias_table"):
+            out[k[:-len("relative_position_bias_table")] + "rel_pos_bias_table"] = v
+        else:
+            out[k] = v
+    if shared is not None:
+        depth = 1 + max(int(k.split(".")[1]) for k in out if k.startswith("blocks."))
+        for i in range(depth):
+            out[f"blocks.{i}.attn.rel_pos_bias_table"] = shared.clone()
+    return out
+
+
+def engine_to_beit(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of beit_to_engine (per-block tables; no ``relative_position_index``, ``head`` or ``mask_token``).  The K third of
+    ``attn.qkv.bias`` must be zero: the layout has no place for it."""
+    out = {}
+    for k, v in sd.items():
+        if k.endswith("attn.qkv.bias"):
+            q, kb, vb = v.chunk(3)
+            if bool((kb != 0).any()):
+                raise ValueError(f"{k}: a non-zero K bias cannot be written in BEiT's q_bias / v_bias layout")
+            out[k[:-len("qkv.bias")] + "q_bias"], out[k[:-len("qkv.bias")] + "v_bias"] = q.clone(), vb.clone()
+        elif k.endswith(".ls1.gamma") or k.endswith(".ls2.gamma"):
+            out[k[:-len("ls1.gamma")] + ("gamma_1" if k.endswith("ls1.gamma") else "gamma_2")] = v
+        elif k.endswith("attn.rel_pos_bias_table"):
+            out[k[:-len("rel_pos_bias_table")] + "relative_position_bias_table"] = v
+        else:
+            out[k] = v
+    return out
+
+
+def random_beit_state_dict(embed_dim=768, depth=12, patch=16, img=224, seed=0, in_chans=3) -> Dict[str, torch.Tensor]:
+    """Seeded random BEiT v2 weights in the ENGINE's layout (used when no local checkpoint exists; ``engine_to_beit`` gives the published
+    one).  ``img``: an int or (height, width).  Blocks as random_dinov2_state_dict's (non-trivial LayerNorm affines and biases) with a zero
+    K bias; relative-position tables ~ N(0, 1) per block, LayerScale gammas 0.1 (1 + 0.5 N(0, 1)), non-zero q / v biases — the reference
+    initialises tables to zero and gammas to a constant, under which a wrong index or a swapped gamma would not show — and ``fc_norm``
+    with gains spread around 1.  No ``pos_embed``."""
+    g = torch.Generator().manual_seed(seed)
+    ih, iw = _pair(img)
+    gh, gw = ih // patch, iw // patch
+    heads = embed_dim // 64
+    sd = {"cls_token": 0.02 * torch.randn(1, 1, embed_dim, generator=g)}
+    bound = 1.0 / math.sqrt(in_chans * patch * patch)
+    sd["patch_embed.proj.weight"] = (torch.rand(embed_dim, in_chans, patch, patch, generator=g) * 2 - 1) * bound
+    sd["patch_embed.proj.bias"] = (torch.rand(embed_dim, generator=g) * 2 - 1) * bound
+    _random_blocks(sd, "blocks.", _TIMM_BLOCK, embed_dim, depth, g)
+    for i in range(depth):
+        p = f"blocks.{i}."
+        sd[p + "attn.qkv.bias"][embed_dim:2 * embed_dim] = 0.0
+        sd[p + "attn.rel_pos_bias_table"] = torch.randn((2 * gh - 1) * (2 * gw - 1) + 3, heads, generator=g)
+        sd[p + "ls1.gamma"] = 0.1 * (1.0 + 0.5 * torch.randn(embed_dim, generator=g))
+        sd[p + "ls2.gamma"] = 0.1 * (1.0 + 0.5 * torch.randn(embed_dim, generator=g))
+    sd["fc_norm.weight"] = 1.0 + 0.1 * torch.randn(embed_dim, generator=g)
+    sd["fc_norm.bias"] = 0.02 * torch.randn(embed_dim, generator=g)
+    return sd
+
+
 def sincos_pos_embed_2d(embed_dim: int, grid_hw, add_cls_token: bool = True) -> np.ndarray:
     """evals/models/utils.py:75-102 + HF get_2d_sincos_pos_embed_from_grid (MAE): half of the
     channels encode the w coordinate ("w goes first"), half the h coordinate; each half is
@@ -499,6 +593,8 @@ class ViTBackbone(nn.Module):
     tap_input_of_block = False
     act = "gelu"  # after fc1: 'gelu' (erf), 'quick_gelu', 'gelu_tanh' (ViTEngine)
     rope_freq = None  # CroCo v2: RoPE<freq> on Q and K of every block (ViTEngine(rope_freq=...)); None: no rotation
+    rel_pos_grid = None  # BEiT: (gh, gw) of the grid the blocks' relative-position bias tables belong to (ViTEngine(rel_pos_grid=...))
+    replay_after_norm = False  # BEiT v2's wrapper: all blocks + fc_norm, then the tapped loop over the blocks again (ViTEngine.forward_taps)
     supports_pipelining = True  # per-slot buffers, tap-BN running-statistics updates deferred to the consumer (mvp/pipeline.py)
     graph_safe = True  # a pipelined forward launches only this library's kernels on fixed buffers: it can be captured in a hipGraph
 
@@ -524,7 +620,7 @@ class ViTBackbone(nn.Module):
         return getattr(self, self.params_attr)
 
     def _signature(self):
-        return tuple((p.data_ptr(), p._version) for p in self._params().parameters()) + (self._precision, self.act, self.rope_freq)
+        return tuple((p.data_ptr(), p._version) for p in self._params().parameters()) + (self._precision, self.act, self.rope_freq, self.rel_pos_grid)
 
     def engine(self) -> ViTEngine:
         sig = self._signature()
@@ -535,7 +631,8 @@ class ViTBackbone(nn.Module):
                 raise lib.MvpError("backbone parameters are on the CPU: call model.to('cuda') — the HIP path has no CPU fallback")
             sd = {k: v for k, v in params.state_dict().items()}
             self._engine_obj = ViTEngine(sd, heads=self.heads, patch=self.patch_size, ln_eps=self.ln_eps, precision=self._precision,
-                                         device=dev, pos_embed_mode=self.pos_embed_mode, act=self.act, rope_freq=self.rope_freq)
+                                         device=dev, pos_embed_mode=self.pos_embed_mode, act=self.act, rope_freq=self.rope_freq,
+                                         rel_pos_grid=self.rel_pos_grid)
             self.n_prefix = self._engine_obj.n_prefix
             self._engine_sig = sig
         return self._engine_obj
@@ -558,7 +655,8 @@ class ViTBackbone(nn.Module):
         bns, mode = self._tap_bn()
         with torch.no_grad():
             taps = eng.forward_taps(images, self.multilayers, bn=bns, bn_mode=mode, tap_input_of_block=self.tap_input_of_block,
-                                    want_cls=want_cls or self.output in ("cls", "dense-cls"), groups=pipeline.current_groups())
+                                    want_cls=want_cls or self.output in ("cls", "dense-cls"), groups=pipeline.current_groups(),
+                                    **({"replay_after_norm": True} if self.replay_after_norm else {}))
             # (num_batches_tracked is incremented by the tap kernel's statistics pass: no extra launch)
         return taps
 

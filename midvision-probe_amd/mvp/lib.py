@@ -71,6 +71,10 @@ class AttentionArgs(C.Structure):
                 ("ld_qkv", _i), ("ld_out", _i), ("scale", _f), ("precision", _i), ("out_layout", _i), ("v_format", _i), ("out_f16", _i)]
 
 
+class AttentionBiasArgs(C.Structure):  # mvp_attention_bias_args: attention with a dense per-head logit bias (added within ABI 8)
+    _fields_ = [("att", AttentionArgs), ("bias", _vp), ("bias_head_stride", _i64), ("ld_bias", _i)]
+
+
 class ClsRowsArgs(C.Structure):
     _fields_ = [("cls", _vp), ("pos0", _vp), ("x", _vp), ("B", _i), ("N", _i), ("C", _i)]
 
@@ -279,12 +283,13 @@ SYMBOLS = {
     "mvp_patch_gather_ld": PatchGatherLdArgs,
     "mvp_prefix_rows": PrefixRowsArgs,
     "mvp_rope2d_qkv": Rope2dQkvArgs,
+    "mvp_attention_bias_fwd": AttentionBiasArgs,
 }
 
 # the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
 NEW_STRUCTS_ABI7 = {"mvp_gemm_scaled_args": GemmScaledArgs, "mvp_patch_gather_ld_args": PatchGatherLdArgs, "mvp_prefix_rows_args": PrefixRowsArgs}
 
-NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs}  # the same for the additions of / within ABI 8
+NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs, "mvp_attention_bias_args": AttentionBiasArgs}  # the same for the additions of / within ABI 8
 
 _lib: Optional[C.CDLL] = None
 

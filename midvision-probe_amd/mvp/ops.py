@@ -279,11 +279,14 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: Opt
 
 
 def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precision: int, ld_qkv=None, ld_out=None, v_f16: bool = False,
-              out_f16: bool = False, qk_f16: bool = False) -> None:
+              out_f16: bool = False, qk_f16: bool = False, bias: Optional[torch.Tensor] = None, ld_bias=None, bias_head_stride=None) -> None:
     """``v_f16``: the V third of ``qkv`` holds hi = fp16, lo = bf16 (``gemm(..., f16_col0=2 * H * 64)``); the probabilities are then held
     as one fp16 value (mvp_attention_args.v_format = MVP_ATT_V_F16; bf16x3 only).  ``out_f16``: the output pair leaves as the activation
     operand of a PREC_F16X2 GEMM (``split_f16_comp``'s form).  ``qk_f16`` (with ``v_f16``): Q and K are the compensated fp16 pairs of
-    ``gemm(..., f16_col0=-2 * H * 64)`` (activation / weight-side form) and Q.K^T runs two f16 products (MVP_ATT_V_F16_QK_F16)."""
+    ``gemm(..., f16_col0=-2 * H * 64)`` (activation / weight-side form) and Q.K^T runs two f16 products (MVP_ATT_V_F16_QK_F16).
+    ``bias``: fp32 [H, N, ld_bias] added to the logits of every image, softmax(Q K^T * scale + bias[h]) (mvp_attention_bias_fwd; natural-log
+    units; ``ld_bias`` >= 64 * ceil(N / 64), default ``bias.stride(1)``; ``bias_head_stride`` default ``bias.stride(0)``; columns >= N may hold
+    anything).  None: mvp_attention_fwd, exactly as before."""
     if qk_f16 and not v_f16:
         raise lib.MvpError("attention: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
     ilv = isinstance(out, IlvPair)
@@ -292,6 +295,13 @@ def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precis
     a = lib.AttentionArgs(lib.ptr(qkv[0]), lib.ptr(qkv[1]), lib.ptr(out[0]), lib.ptr(out[1]), B, N, H,
                           ld_qkv if ld_qkv is not None else 3 * H * 64, ld_out if ld_out is not None else H * 64, scale, precision,
                           lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE, (2 if qk_f16 else 1) if v_f16 else 0, 1 if out_f16 else 0)
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.dim() != 3 or bias.stride(2) != 1:
+            raise lib.MvpError("attention: bias must be fp32 [H, N, ld_bias] with unit column stride")
+        ab = lib.AttentionBiasArgs(a, lib.ptr(bias), bias_head_stride if bias_head_stride is not None else bias.stride(0),
+                                   ld_bias if ld_bias is not None else bias.stride(1))
+        _traced("attention", "4x32q bias", precision, 4.0 * B * H * N * N * 64, lambda: lib.call("mvp_attention_bias_fwd", ab))
+        return
     _traced("attention", "4x32q", precision, 4.0 * B * H * N * N * 64, lambda: lib.call("mvp_attention_fwd", a))
 
 

@@ -6,6 +6,9 @@ DINOv2 (ViT-B/14, B/14 with registers, L/14) runs on the same engine: R register
 rows per image, written by mvp_prefix_rows), LayerScale vectors (blocks.i.ls1.gamma / ls2.gamma) are applied in the proj / fc2 epilogues
 (mvp_gemm_scaled), and the 14x14 patches are gathered into zero-padded rows (mvp_patch_gather_ld) against zero-padded weights.
 
+BEiT v2 runs on it too: no position table, a learned relative-position bias per block expanded once into a dense [H, N, ld] array and
+added to the attention logits (mvp_attention_bias_fwd; ``rel_pos_grid``), and the reference wrapper's replay pass (``replay_after_norm``).
+
 Data layout in HBM (per batch of B images, N = n_prefix + gh*gw tokens, n_prefix = 1 + R, M = B*N rows):
   x        fp32  [M, C]      residual stream (kept fp32: LN statistics and residual adds)
   xn       bf16 pair [M, C]  LayerNorm output = A operand of the next GEMM
@@ -149,10 +152,40 @@ def plan_taps(Bt: int, groups) -> Tuple[int, int, int, int]:
     return G, B, carry, tail
 
 
+def rel_pos_index(gh: int, gw: int) -> torch.Tensor:
+    """BEiT's relative-position index for a gh x gw grid behind one class token: int64 [N, N], N = 1 + gh * gw, row = query, column = key,
+    into a table of (2gh - 1)(2gw - 1) + 3 rows.  Patch tokens are row-major (p = y * gw + x); query (yq, xq) against key (yk, xk) reads
+    row (yq - yk + gh - 1) * (2gw - 1) + (xq - xk + gw - 1); the last three rows are cls -> token, token -> cls and cls -> cls
+    (the reference's rule: evals/models/impl_utils/beit_model.py:117-140)."""
+    n = (2 * gh - 1) * (2 * gw - 1) + 3
+    y, x = torch.arange(gh).repeat_interleave(gw), torch.arange(gw).repeat(gh)
+    idx = torch.empty(1 + gh * gw, 1 + gh * gw, dtype=torch.int64)
+    idx[1:, 1:] = (y[:, None] - y[None, :] + gh - 1) * (2 * gw - 1) + (x[:, None] - x[None, :] + gw - 1)
+    idx[0, :] = n - 3
+    idx[:, 0] = n - 2
+    idx[0, 0] = n - 1
+    return idx
+
+
+def dense_rel_pos_bias(table: torch.Tensor, gh: int, gw: int, ld: Optional[int] = None) -> torch.Tensor:
+    """A relative-position table [(2gh - 1)(2gw - 1) + 3, H] -> the dense fp32 [H, N, ld] array mvp_attention_bias_fwd reads
+    (bias[h][q][k] = table[rel_pos_index[q][k]][h]; natural-log units, the kernel folds log2 e itself), on the CPU.  ``ld``: the padded row
+    length, default 64 * ceil(N / 64); padding columns are zero (the kernel may read them and never uses them)."""
+    N = 1 + gh * gw
+    if table.dim() != 2 or table.shape[0] != (2 * gh - 1) * (2 * gw - 1) + 3:
+        raise lib.MvpError(f"relative-position table of {tuple(table.shape)} does not belong to a {gh} x {gw} grid "
+                           f"({(2 * gh - 1) * (2 * gw - 1) + 3} rows expected): re-interpolating tables to another grid is not supported")
+    ld = ld if ld is not None else 64 * ((N + 63) // 64)
+    t = table.detach().to("cpu", torch.float32)
+    out = torch.zeros(t.shape[1], N, ld, dtype=torch.float32)
+    out[:, :, :N] = t[rel_pos_index(gh, gw).reshape(-1)].reshape(N, N, -1).permute(2, 0, 1)
+    return out
+
+
 class ViTEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, heads: int, patch: int = 16, ln_eps: float = 1e-6,
                  precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True, act: str = "gelu",
-                 rope_freq: Optional[float] = None):
+                 rope_freq: Optional[float] = None, rel_pos_grid: Optional[Tuple[int, int]] = None):
         """``state_dict`` in the DINO / timm layout; DINOv2's extras are picked up from it: ``register_tokens`` [1, R, C] (then
         n_prefix = 1 + R) and ``blocks.i.ls1.gamma`` / ``blocks.i.ls2.gamma`` (LayerScale, fused into the proj / fc2 epilogues).
         So are CLIP's and SigLIP's: ``norm_pre.weight`` / ``norm_pre.bias`` (a LayerNorm over the residual stream before block 0, in place),
@@ -165,7 +198,13 @@ class ViTEngine:
         act: the activation after fc1: 'gelu' (erf), 'quick_gelu' (x sigmoid(1.702 x): OpenAI CLIP) or 'gelu_tanh' (SigLIP).
         rope_freq: CroCo v2's RoPE<freq> (100.0 for the published models): Q and K of every block are rotated by the token's (y, x) grid
         position (mvp_rope2d_qkv, between the qkv GEMM — which then writes fp32 — and attention).  The state dict may then come without
-        ``pos_embed`` (C is read from the patch-embedding weight and ``tokens`` adds no position residual)."""
+        ``pos_embed`` (C is read from the patch-embedding weight and ``tokens`` adds no position residual).
+        rel_pos_grid: BEiT's relative-position bias.  (gh, gw) of the ONE grid the model runs at — explicit, because a table's length does
+        not determine a non-square grid; every block's ``blocks.i.attn.rel_pos_bias_table`` [(2gh - 1)(2gw - 1) + 3, H] is expanded here, on
+        the CPU in fp32, into the dense [H, N, ld] array that attention adds to its logits (``dense_rel_pos_bias``; blocks with identical
+        tables share one array).  Such a model may have a class token and no ``pos_embed`` (the class row is ``cls_token`` alone, the patch
+        rows get no position residual), and a forward at another grid raises.  ``fc_norm.weight`` / ``fc_norm.bias`` (BEiT's final norm)
+        are kept for ``forward_taps(..., replay_after_norm=True)``."""
         self.device = torch.device(device)
         self.precision = parse_precision(precision)
         # 'f16x2': a bf16x3 engine (buffers, patch embedding, attention, taps) whose four block GEMMs run two products (lib.PREC_F16X2)
@@ -188,8 +227,10 @@ class ViTEngine:
         sd = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in state_dict.items()}
         self.has_cls = "cls_token" in sd
         self.rope_freq = None if rope_freq is None else float(rope_freq)
-        if "pos_embed" not in sd and (self.rope_freq is None or self.has_cls):
-            raise lib.MvpError("state dict without pos_embed: only a RoPE model without a class token has none (rope_freq=...)")
+        self.rel_pos_grid = None if rel_pos_grid is None else (int(rel_pos_grid[0]), int(rel_pos_grid[1]))
+        if "pos_embed" not in sd and (self.rope_freq is None or self.has_cls) and self.rel_pos_grid is None:
+            raise lib.MvpError("state dict without pos_embed: only a RoPE model without a class token (rope_freq=...) or a model with "
+                               "relative-position bias tables (rel_pos_grid=...) has none")
         self.C = sd["cls_token"].shape[-1] if self.has_cls else sd["pos_embed"].shape[-1] if "pos_embed" in sd else sd["patch_embed.proj.weight"].shape[0]
         if self.C != heads * 64:
             raise lib.MvpError(f"attention kernel requires head_dim 64 (C={self.C}, heads={heads})")
@@ -215,6 +256,7 @@ class ViTEngine:
         self.w_patch = ops.split_bf16(pw2, self.precision)
         self.b_patch = sd.get("patch_embed.proj.bias")  # (CLIP's patch convolution has none)
         self.blocks = []
+        self._bias_tables: List[Tuple[torch.Tensor, torch.Tensor]] = []  # (table on the CPU, its dense [H, N, ld] bias on the device)
         for i in range(self.depth):
             p = f"blocks.{i}."
             blk = dict(
@@ -233,7 +275,11 @@ class ViTEngine:
             if self.precision == PREC_BF16X3:  # hi|lo-interleaved copies of the frozen weights for the large-M GEMM kernel (mvp.ops.interleave_pair)
                 for n in ("qkv_w", "proj_w", "fc1_w", "fc2_w"):
                     blk[n + "_ilv"] = ops.interleave_pair(blk[n])
+            if self.rel_pos_grid is not None:
+                blk["att_bias"] = self._dense_bias(state_dict[p + "attn.rel_pos_bias_table"])
             self.blocks.append(blk)
+        self.fc_norm = (sd["fc_norm.weight"], sd["fc_norm.bias"]) if "fc_norm.weight" in sd else None  # BEiT's final norm (replay_after_norm)
+        self._zero_c = torch.zeros(self.C, dtype=torch.float32, device=self.device) if self.pos_embed is None and self.has_cls else None
         self.hidden = self.blocks[0]["fc1_b"].numel()
         self._buffers = EngineBuffers()  # everything a forward reuses, per pipeline slot (mvp/buffers.py)
         self._pos: Dict[Tuple[int, int], torch.Tensor] = {}
@@ -241,6 +287,20 @@ class ViTEngine:
         pipeline.publish()  # the split weights are read by forwards on any stream
 
     # ------------------------------------------------------------------ helpers
+    def _dense_bias(self, table: torch.Tensor) -> torch.Tensor:
+        """The dense logit bias of one block's table on the device; a table equal to one seen before shares its array."""
+        if not self.has_cls:
+            raise lib.MvpError("relative-position bias tables: the index rule has a class token (cls_token missing)")
+        if table.dim() != 2 or table.shape[1] != self.heads:
+            raise lib.MvpError(f"relative-position table of {tuple(table.shape)}: [rows, heads = {self.heads}] expected")
+        t = table.detach().to("cpu", torch.float32)
+        for seen, dense in self._bias_tables:
+            if torch.equal(seen, t):
+                return dense
+        dense = dense_rel_pos_bias(t, *self.rel_pos_grid).to(self.device)
+        self._bias_tables.append((t, dense))
+        return dense
+
     def _workspace(self, B: int, gh: int, gw: int, headroom: int = 0) -> dict:
         def alloc():
             N = self.n_prefix + gh * gw
@@ -272,7 +332,8 @@ class ViTEngine:
         maps), the carry stores and the position tables.  A captured hipGraph of that slot's forward holds their raw addresses: the
         pipeline keeps this list alive with the graph, because the engine itself drops the buffers of other resolutions when a new one
         arrives."""
-        return self._buffers.snapshot(slot) + list(self._pos.values()) + [t for cs in self._rope.values() for t in cs]
+        return (self._buffers.snapshot(slot) + list(self._pos.values()) + [t for cs in self._rope.values() for t in cs] +
+                [dense for _, dense in self._bias_tables])
 
     def rope_for(self, gh: int, gw: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The cos / sin tables of RoPE<rope_freq> for a gh x gw grid, fp32 [max(gh, gw), 32], row = grid coordinate: the reference's
@@ -343,6 +404,9 @@ class ViTEngine:
         else:  # center_padding quirk: a non-ragged dim still gets a full patch (utils.py:55-72)
             ph, pw = P - rh, P - rw
         gh, gw = (H + ph) // P, (W + pw) // P
+        if self.rel_pos_grid is not None and (gh, gw) != self.rel_pos_grid:
+            raise lib.MvpError(f"images of {H} x {W} make a {gh} x {gw} token grid; this model's relative-position bias was built for "
+                               f"{self.rel_pos_grid[0]} x {self.rel_pos_grid[1]} (rel_pos_grid)")
         ws = self._workspace(B, gh, gw, headroom)
         npre, C = self.n_prefix, self.C
         N = npre + gh * gw
@@ -351,16 +415,16 @@ class ViTEngine:
             ops.patch_gather(images, ws["patches"], P, gh, gw, ph // 2, pw // 2)
         else:
             ops.patch_gather_ld(images, ws["patches"], P, gh, gw, ph // 2, pw // 2, Kp)
-        pos = self.pos_for(gh, gw, H + ph, W + pw) if self.pos_embed is not None else None  # (None: RoPE, nothing to add here)
+        pos = self.pos_for(gh, gw, H + ph, W + pw) if self.pos_embed is not None else None  # (None: RoPE / relative-position bias, nothing to add here)
         # x[b, npre+p, :] = patches · Wᵀ + bias + pos[1+p]   (row remap skips the CLS / register slots)
-        ops.gemm(ws["patches"], self.w_patch, B * gh * gw, C, Kp, bias=self.b_patch, residual=pos[1:] if self.has_cls else pos, out_f32=ws["x"],
+        ops.gemm(ws["patches"], self.w_patch, B * gh * gw, C, Kp, bias=self.b_patch, residual=pos[1:] if (self.has_cls and pos is not None) else pos, out_f32=ws["x"],
                  precision=self.precision, row_group=gh * gw, row_group_stride=N, row_group_off=npre, res_row_mod=gh * gw if pos is not None else 0)
         if self.rope_freq is not None:
             self.rope_for(gh, gw)  # (built and published here, before any block runs)
         if not self.has_cls:
             pass  # no prefix rows at all (SigLIP)
         elif self.reg is None:
-            ops.cls_rows(self.cls, pos, ws["x"], B, N, C)
+            ops.cls_rows(self.cls, pos if pos is not None else self._zero_c, ws["x"], B, N, C)  # (no table: the class row is cls alone)
         else:
             ops.prefix_rows(self.cls, pos, self.reg, ws["x"], B, N, C)
         if self.pre_norm is not None:  # CLIP's ln_pre: every row of the residual stream, in place
@@ -406,7 +470,7 @@ class ViTEngine:
             self._check_f16_range(f"block {i}: LayerNorm 1 output", ws["xn"], M)
         if chk and qk16:
             self._check_f16_range(f"block {i}: Q / K", (ws["qkv"][0][:, :2 * C], ws["qkv"][1][:, :2 * C]), M)
-        ops.attention(ws["qkv"], ws["ao"], B, N, self.heads, 64 ** -0.5, pr, v_f16=vf16, qk_f16=qk16, out_f16=f2)
+        ops.attention(ws["qkv"], ws["ao"], B, N, self.heads, 64 ** -0.5, pr, v_f16=vf16, qk_f16=qk16, out_f16=f2, bias=blk.get("att_bias"))
         if chk:
             self._check_f16_range(f"block {i}: attention output", ws["ao"], M)
         ops.gemm(ws["ao"], blk["proj_w"], M, C, C, bias=blk["proj_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("proj_w_ilv"),
@@ -422,7 +486,8 @@ class ViTEngine:
                  col_scale=blk["ls2"])
 
     def forward_taps(self, images: torch.Tensor, layers: Sequence[int], *, bn: Optional[Sequence[dict]] = None,
-                     bn_mode: int = 0, pack: bool = True, tap_input_of_block: bool = False, want_cls: bool = False, groups: int = 1):
+                     bn_mode: int = 0, pack: bool = True, tap_input_of_block: bool = False, want_cls: bool = False, groups: int = 1,
+                     replay_after_norm: bool = False):
         """Run blocks up to the last tapped one; at each tap apply the (train-mode) tap BN and
         emit the NCHW map (+ token-major packing).  ``bn[j]`` = dict(weight,bias,running_mean,
         running_var) tensors or None; bn_mode: 0 train stats, 1 eval, 2 no norm.
@@ -438,7 +503,10 @@ class ViTEngine:
         the stream's carry store, written by the previous span's forward on the same stream) are copied in FRONT of this span's rows — the
         ``x`` workspace has that head-room — so that all complete batches are contiguous and one grouped tap-BN launch serves them, and
         the rows of a trailing incomplete batch are copied to the carry store for the next span.  Returns ``TapGroups`` of the
-        (carry + images) // batch batches this forward completes."""
+        (carry + images) // batch batches this forward completes.
+        ``replay_after_norm`` (BEiT v2's wrapper, beit_v2.py:261-265): before the tapped loop, run ALL ``depth`` blocks over the token
+        stream and apply ``fc_norm`` to every row of it in place; the tapped loop then runs the blocks AGAIN on that result.  Blocks and
+        LayerNorm are per row, so grouped and span forwards and graph capture need nothing new."""
         if want_cls and not self.has_cls:
             raise lib.MvpError("want_cls: this model has no CLS token (n_prefix = 0); use output 'dense' or 'gap'")
         span = groups if isinstance(groups, pipeline.Span) else None
@@ -452,6 +520,12 @@ class ViTEngine:
             raise lib.MvpError("a grouped forward with train-mode tap BN must run under the pipeline (its running-statistics updates are per batch)")
         ws, Bt, gh, gw = self.tokens(images, headroom=span.batch if span else 0)
         N = self.n_prefix + gh * gw
+        if replay_after_norm:
+            if self.fc_norm is None:
+                raise lib.MvpError("replay_after_norm: the state dict has no fc_norm.weight / fc_norm.bias")
+            for i in range(self.depth):
+                self.run_block(i, ws, Bt, N)
+            ops.layernorm(ws["x"], self.fc_norm[0], self.fc_norm[1], None, Bt * N, self.C, self.ln_eps, out_f32=ws["x"])
         x_bn, store, bn_ws, packs, out = self._tap_buffers(ws, span, G, B, carry, gh, gw, layers, pack, want_cls)
         t = SimpleNamespace(ws=ws, x_bn=x_bn, store=store, bn_ws=bn_ws, packs=packs, out=out, Bt=Bt, N=N, hw=gh * gw, G=G, B=B, carry=carry, tail=tail,
                             bn=bn, bn_mode=bn_mode, want_cls=want_cls, defer=defer, outs=[TapOutputs() for _ in range(G)],

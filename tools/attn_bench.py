@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Attention microbenchmark + ablation (diagnostic).  Builds ablated copies of attention.hip under
 gpurun_out/ and times the hot-path shape with HIP events, interleaved rounds in one process.
-ablate: 0 full, 1 no softmax VALU, 2 no PV MFMAs, 3 no S MFMAs, 4 no K/V staging, 5 no tiles (prologue+epilogue)."""
+ablate: 0 full, 1 no softmax VALU, 2 no PV MFMAs, 3 no S MFMAs, 4 no K/V staging, 5 no tiles (prologue+epilogue).
+--bias: instead, the shipped library's mvp_attention_bias_fwd (a dense fp32 [H, N, ld] logit bias) against mvp_attention_fwd on the same
+operands, alternating, at N = 197 and 577 (env N="197 577"), B from env B (default 110), H = 12, every bf16x3 operand form."""
 import ctypes as C, os, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "midvision-probe_amd"))
@@ -28,7 +30,42 @@ def build(ablate, extra="", src=None, tag=""):
     return l
 
 
+def bias_ab():
+    """Biased against unbiased attention: same build, same buffers, three alternations of 20 launches each; min and median per variant."""
+    import statistics
+    dev = torch.device("cuda")
+    B = int(os.environ.get("B", 110)); H = 12
+    so = lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    for N in (int(n) for n in os.environ.get("N", "197 577").split()):
+        ld = 64 * ((N + 63) // 64)
+        bias = torch.randn(H, N, ld, device=dev)
+        qkv = ops.split_bf16(torch.randn(B * N, 3 * H * 64, device=dev) * 0.5, 3)
+        out = ops.empty_pair((B * N, H * 64), 3, dev)
+        for vf, form in ((2, "bf16x3_vf16_qk16"), (1, "bf16x3_vf16"), (0, "bf16x3")):
+            att = lib.AttentionArgs(qkv[0].data_ptr(), qkv[1].data_ptr(), out[0].data_ptr(), out[1].data_ptr(), B, N, H, 3 * H * 64, H * 64, 0.125, 3, 0, vf, 0)
+            ab = lib.AttentionBiasArgs(att, bias.data_ptr(), N * ld, ld)
+            calls = {"plain": lambda: so.mvp_attention_fwd(C.byref(att), st), "bias": lambda: so.mvp_attention_bias_fwd(C.byref(ab), st)}
+            res = {}
+            for rnd in range(3):
+                for vn, fn in calls.items():
+                    for _ in range(3):
+                        assert fn() == 0
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(20):
+                        fn()
+                    e1.record(); torch.cuda.synchronize()
+                    res.setdefault(vn, []).append(e0.elapsed_time(e1) / 20 * 1e3)
+            mp, mb = statistics.median(res["plain"]), statistics.median(res["bias"])
+            print(f"B={B} N={N} H={H} {form}: plain {mp:7.1f} us (rounds {' '.join(f'{x:.1f}' for x in res['plain'])})  "
+                  f"bias {mb:7.1f} us (rounds {' '.join(f'{x:.1f}' for x in res['bias'])})  bias / plain = {mb / mp:.3f}  "
+                  f"bias array {H * N * ld * 4 / 1e6:.2f} MB", flush=True)
+
+
 def main():
+    if "--bias" in sys.argv:
+        return bias_ab()
     names = {0: "full", 1: "no_softmax", 2: "no_pv", 3: "no_s", 4: "no_stage", 5: "no_tiles"}
     variants = {names[a]: build(a) for a in names}
     prev = os.path.join(REPO, "tools", "micro", "attention_prev.hip")

@@ -26,7 +26,9 @@ import torch  # noqa: E402
 MODELS = {"dino_b16": ("dino", "vitb16", "dense"), "dinov2_b14": ("dinov2", "vitb14", "dense-cls"),
           "dinov2_b14_reg": ("dinov2", "vitb14_reg", "dense-cls"), "dinov2_l14": ("dinov2", "vitl14", "dense-cls"),
           # the same GEMMs; crocov2 adds mvp_rope2d_qkv and the fp32 qkv output per block
-          "croco_b16": ("croco", "vitb16", "dense"), "crocov2_b16": ("crocov2", "vitb16", "dense")}
+          "croco_b16": ("croco", "vitb16", "dense"), "crocov2_b16": ("crocov2", "vitb16", "dense"),
+          # 24 block passes per forward (all blocks + fc_norm, then the tapped pass) with a logit bias in attention
+          "beit-v2_vitb16": ("beit_v2", "vitb16", "dense")}
 
 
 def build(name, precision, dev):
@@ -43,6 +45,10 @@ def build(name, precision, dev):
             from evals.models.crocov2 import CROCOV2
 
             model = (CROCO if dn == "croco" else CROCOV2)(model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
+        elif dn == "beit_v2":
+            from evals.models.beit_v2 import BEiTV2
+
+            model = BEiTV2(model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
         else:
             model = DINO(dino_name=dn, model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
     torch.manual_seed(0)
