@@ -77,6 +77,9 @@ typedef struct {
                                 Added within 8: mvp_rope2d_qkv (a new export with its own tagged argument struct; no existing struct changed).
                                 Added within 8: mvp_attention_bias_fwd (attention with a dense per-head additive logit bias; a new export with its own
                                 tagged argument struct that wraps mvp_attention_args unchanged).
+                                Added within 8: mvp_gather_rows (row gather of 16-bit pair buffers by an index table), mvp_relpos_terms (SAM's
+                                decomposed relative-position terms of the unscaled q) and mvp_attention_relpos_fwd (attention with that decomposed
+                                bias); three new exports, each with its own tagged argument struct, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -349,6 +352,77 @@ struct mvp_rope2d_qkv_args {
   int precision, v_format;     /* as mvp_attention_args: which 16-bit form each third gets          */
 };
 int mvp_rope2d_qkv(const mvp_rope2d_qkv_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)
+ * Row gather of a 16-bit pair buffer by an int32 index table (SAM's window partition and un-partition):
+ *     out[r][0 .. cols) = idx[r] >= 0 ? in[idx[r]][0 .. cols) : 0          r in [0, rows)
+ * a pure copy, bit for bit, of ``cols`` 16-bit elements per row of in_hi -> out_hi and (when both are given) in_lo -> out_lo.  An
+ * interleaved pair (MVP_PAIR_A_ILV32: ONE array of 2 C elements per row) is gathered as in_hi / out_hi with cols = 2 C and in_lo =
+ * out_lo = NULL.  An index >= rows_in gives a zero row too (no row beyond the input is ever read).  in and out must not overlap.
+ * MVP_EINVAL: NULL in_hi / out_hi / idx, in_lo without out_lo or the reverse, rows <= 0, rows_in <= 0, cols <= 0 or cols % 8 != 0,
+ * ld_in or ld_out < cols or % 8 != 0, a pointer not 16-byte aligned (idx: 4-byte), rows * (cols / 8) >= 2^31.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_gather_rows_args mvp_gather_rows_args;
+struct mvp_gather_rows_args {
+  const mvp_bf16* in_hi; const mvp_bf16* in_lo;   /* [rows_in, ld_in]; in_lo may be NULL (then out_lo must be NULL) */
+  mvp_bf16* out_hi; mvp_bf16* out_lo;             /* [rows, ld_out]                                                  */
+  const int* idx;                                 /* [rows] int32: source row, < 0 = zero row                        */
+  int rows, rows_in, cols;                        /* cols: 16-bit elements copied per row, % 8 == 0                  */
+  int ld_in, ld_out;                              /* elements, % 8 == 0, >= cols                                     */
+};
+int mvp_gather_rows(const mvp_gather_rows_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)
+ * SAM's decomposed relative-position terms (segment_anything's add_decomposed_rel_pos) of the UNSCALED q, in natural-log units.
+ * Sits between the qkv GEMM and mvp_attention_relpos_fwd, like mvp_rope2d_qkv: reads the projection as fp32 [M, ld_in] (the GEMM's
+ * out_f32 form), and writes
+ *   (1) rel[(b * H + h) * rel_bh_stride + q * ld_rel + j], b = m / N, q = m % N, (yq, xq) = (q / Qw, q % Qw):
+ *         j in [0, Kh):        sum_d q[b, h, q, d] * rh[yq][j][d]
+ *         j in [Kh, Kh + Kw):  sum_d q[b, h, q, d] * rw[xq][j - Kh][d]
+ *       accumulated in fp32 with fma, d = 0 .. 63 in order; columns j >= Kh + Kw of a row are not written;
+ *   (2) the pair buffer the attention kernels read: every third of the projection in exactly the 16-bit form the qkv GEMM's epilogue
+ *       writes for the same (precision, v_format), as mvp_rope2d_qkv does (Q, K and V all pass through unchanged).
+ * rh is fp32 [Qh][Kh][64], rw fp32 [Qw][Kw][64]; both are shared by all heads and images.
+ * MVP_EINVAL: NULL pointers (out_lo may be NULL under MVP_PREC_BF16 only), M % N != 0, Qh * Qw != N, Kh or Kw <= 0,
+ * ld_rel < Kh + Kw or ld_rel % 4 != 0, rel_bh_stride < N * ld_rel, ld_in or ld_out < 3 * H * 64, rows not 16-byte aligned (pointers % 16,
+ * ld_in % 4, ld_out % 8), H > 256 (the Q row of a token is held in LDS: H * 256 bytes), precision / v_format as mvp_rope2d_qkv.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_relpos_terms_args mvp_relpos_terms_args;
+struct mvp_relpos_terms_args {
+  const float* qkv;            /* [M, ld_in] fp32, col = which*H*64 + head*64 + d                   */
+  mvp_bf16* out_hi; mvp_bf16* out_lo;  /* [M, ld_out] pair, MVP_PAIR_SEPARATE                       */
+  float* rel;                  /* [B*H][N][ld_rel] fp32                                             */
+  const float* rh; const float* rw;    /* [Qh][Kh][64], [Qw][Kw][64] fp32                           */
+  int64_t rel_bh_stride;       /* elements; >= N * ld_rel                                           */
+  int M, N, H;                 /* rows, tokens per image (window), heads; M % N == 0                */
+  int Qh, Qw, Kh, Kw;          /* query grid (Qh * Qw == N) and key grid                            */
+  int ld_in, ld_out, ld_rel;
+  int precision, v_format;     /* as mvp_attention_args: which 16-bit form each third gets          */
+};
+int mvp_relpos_terms(const mvp_relpos_terms_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)
+ * Attention with a decomposed relative-position bias on the logits (SAM's image encoder):
+ *   O = softmax(Q K^T * att.scale + rel[bh][q][k / Kw] + rel[bh][q][Kh + k % Kw]) V,       bh = b * H + h, N == Kh * Kw
+ * with rel as mvp_relpos_terms writes it (fp32, natural-log units, finite).  The bias differs per image, head and query, so no [N, N]
+ * array of it exists anywhere: a query row's Kh + Kw values are read as they are needed.  Everything else as mvp_attention_fwd (same
+ * kernels, same operand forms, same N <= 256 resident / streaming split).  Only columns [0, Kh + Kw) of rows q < N of pairs
+ * bh < B * H are read.
+ * MVP_EINVAL: everything mvp_attention_fwd rejects; rel NULL or not 4-byte aligned; Kh or Kw <= 0 or Kh * Kw != N;
+ * ld_rel < Kh + Kw; rel_bh_stride < N * ld_rel; N * ld_rel >= 2^30 (a row's byte offset inside a pair is a 32-bit lane offset).
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_attention_relpos_args mvp_attention_relpos_args;
+struct mvp_attention_relpos_args {
+  mvp_attention_args att;      /* everything as mvp_attention_fwd */
+  const float* rel;            /* fp32 [B*H][N][ld_rel] */
+  int64_t rel_bh_stride;       /* elements; >= N * ld_rel */
+  int ld_rel;                  /* elements; >= Kh + Kw */
+  int Kh, Kw;                  /* key grid; Kh * Kw == N */
+};
+int mvp_attention_relpos_fwd(const mvp_attention_relpos_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * CLS row writer: x[b, 0, :] = cls[:] + pos[0, :]   (ibot_transformers.py:347-352).

@@ -40,6 +40,12 @@
 // a BIAS kernel's argument is mvp_attention_bias_args (mvp_attention_args + a dense fp32 [H][N][ld] logit bias).  Every bias path is under
 // ``if constexpr``, so the BIAS = false instantiations are the kernels of mvp_attention_fwd, instruction for instruction
 // (profiles/attention_bias_kernel_resources.txt).  See AttnBias below.
+// BIAS == 2 (mvp_attention_relpos_fwd; SAM's decomposed relative-position bias): the parameter is an int, 0 = none, 1 = the dense bias,
+// 2 = bias[q][k] = rel[bh][q][k / Kw] + rel[bh][q][Kh + k % Kw] with rel the fp32 [B*H][N][ld_rel] output of mvp_relpos_terms; the kernel
+// argument is mvp_attention_relpos_args.  The bias differs per image, head and query, so it is never densified: a lane reads the two
+// terms of each of its keys as cached 4-byte loads from its query's row of rel (Kh + Kw floats: one or two cache lines at a 14 x 14
+// window, all of a lane's loads of a tile and of every tile hit the same lines), issued after the Q.K^T cluster, where they are used.
+// Everything downstream of ``s * scale + bias`` is the BIAS == 1 code.  (profiles/attention_relpos_kernel_resources.txt)
 #include "mvp_common.h"
 
 #ifndef MVP_ATT_NT
@@ -91,12 +97,19 @@ struct AttnState {
 // test of the VF16 forms, exp2 and the row sum all act on the biased value, through the very code of the unbiased kernels.
 // Padding columns (k >= N, may hold NaN) fall to the key mask, which selects; all-padding sub-tiles are not loaded at all.
 // The diagnostic knobs apply as they stand (MVP_ATT_ABLATE 1 / 3 drop the softmax / the Q.K^T products, not the bias load and fma).
+// BIAS == 2: key k of the grid is (ky, kx) = (k / Kw, k % Kw).  A lane's 4 consecutive keys may straddle one or more key-grid rows
+// (Kw % 4 != 0, or Kw < 4), so (ky, kx) is stepped key by key with a wrap at Kw — exact for every Kw >= 1; ONE division per tile gives
+// the lane's first key, the sub-tiles 16 keys further follow by (q16, r16) = (16 / Kw, 16 % Kw).  Keys >= N of the LAST tile read
+// (0, 0) instead (inside the row; the key mask discards them) and all-padding sub-tiles read nothing.
 struct AttnBias {
-  const float* row[2];  // per qt: bias + h * head_stride + min(q, N - 1) * ld_bias + g * 4
+  const float* row[2];  // BIAS 1, per qt: bias + h * head_stride + min(q, N - 1) * ld_bias + g * 4
   float scale;
+  const float* rel;     // BIAS 2: rel + bh * rel_bh_stride (wave-uniform: the loads take it as a scalar base + a 32-bit lane offset)
+  unsigned qoff[2];     // BIAS 2, per qt: BYTE offset of row min(q, N - 1) in the pair, 4 * q * ld_rel (N * ld_rel < 2^30, host check)
+  int Kh, Kw, q16, r16;  // BIAS 2 (q16, r16 in bytes: 4 * (16 / Kw), 4 * (16 % Kw))
 };
 
-template <int SPLIT, bool LAST, int VF16 = 0, bool BIAS = false>
+template <int SPLIT, bool LAST, int VF16 = 0, int BIAS = 0>
 __device__ __forceinline__ void attn_tile(AttnState<SPLIT>& st, const char* kb, const char* vb, int key0, int N, float cs, int lane,
                                           const AttnBias& ab = AttnBias{}) {
   static_assert(!VF16 || SPLIT == 3, "the fp16-probability form belongs to the bf16x3 mode");
@@ -110,7 +123,7 @@ __device__ __forceinline__ void attn_tile(AttnState<SPLIT>& st, const char* kb, 
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) s[t][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   f32x4_t bv[4][2];
-  if constexpr (BIAS) {
+  if constexpr (BIAS == 1) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -153,13 +166,51 @@ __device__ __forceinline__ void attn_tile(AttnState<SPLIT>& st, const char* kb, 
     }
   }
   ATT_PRIO(0);
-  if constexpr (BIAS) {
+  if constexpr (BIAS == 1) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) s[t][qt][j] = __builtin_fmaf(s[t][qt][j], ab.scale, bv[t][qt][j]);
+  }
+  if constexpr (BIAS == 2) {  // s <- s * scale + rel[q][ky] + rel[q][Kh + kx], the two terms read here (nothing of them is live under the MFMA cluster)
+    unsigned k0 = (unsigned)(key0 + g * 4);
+    // (opaque to the optimiser: the offsets of a tile whose key0 is a constant — tile 0 of the resident kernel — are otherwise computed
+    //  once in front of the pair loop and kept, 64 of them, in registers the kernel does not have)
+    asm volatile("" : "+v"(k0));
+    const unsigned Kw4 = (unsigned)ab.Kw << 2, Kh4 = (unsigned)ab.Kh << 2;
+    const unsigned q0y = k0 / (unsigned)ab.Kw;
+    unsigned ty = q0y << 2, tx = (k0 - q0y * (unsigned)ab.Kw) << 2;  // BYTE offsets of (ky, kx) of the lane's first key of sub-tile t
+    const char* base = (const char*)ab.rel;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (!(LAST && t >= nsub)) {  // (an all-padding sub-tile reads nothing; the key mask below replaces its scores)
+        unsigned ky = ty, kx = tx;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const bool dead = LAST && (int)k0 + t * 16 + j >= N;  // reads (0, 0): nothing beyond column Kh + Kw - 1 of the row is read
+          const unsigned yy = dead ? 0u : ky, xx = (dead ? 0u : kx) + Kh4;
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt)  // 32-bit byte offsets on a scalar base
+            s[t][qt][j] = __builtin_fmaf(s[t][qt][j], ab.scale, *(const float*)(base + (ab.qoff[qt] + yy)) + *(const float*)(base + (ab.qoff[qt] + xx)));
+          kx += 4;
+          if (kx == Kw4) {
+            kx = 0;
+            ky += 4;
+          }
+        }
+      }
+      ty += ab.q16;
+      tx += ab.r16;
+      if (tx >= Kw4) {
+        tx -= Kw4;
+        ty += 4;
+      }
+      // one sub-tile's 16 loads at a time: left alone, the scheduler issues all 64 loads of the tile first (64 offsets + 64 results
+      // live at once) and the resident kernels (256 registers a lane at 8 waves) spill
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   // ---------------- online softmax (q on the lane; keys on registers + lane groups)
   const int kbase = key0 + g * 4;
@@ -360,20 +411,40 @@ __device__ __forceinline__ void attn_stage_piece(const mvp_attention_args& p, si
 }
 
 // Kernel argument of the two kernels: the plain struct, or (BIAS) the struct that wraps it (its first member).
-template <bool BIAS> struct AttnKArgs { typedef mvp_attention_args type; };
-template <> struct AttnKArgs<true> { typedef mvp_attention_bias_args type; };
+template <int BIAS> struct AttnKArgs { typedef mvp_attention_args type; };
+template <> struct AttnKArgs<1> { typedef mvp_attention_bias_args type; };
+template <> struct AttnKArgs<2> { typedef mvp_attention_relpos_args type; };
 __host__ __device__ __forceinline__ const mvp_attention_args& att_of(const mvp_attention_args& a) { return a; }
 __host__ __device__ __forceinline__ const mvp_attention_args& att_of(const mvp_attention_bias_args& a) { return a.att; }
+__host__ __device__ __forceinline__ const mvp_attention_args& att_of(const mvp_attention_relpos_args& a) { return a.att; }
 // The bias row pointers of this lane's two query rows (clamped like the Q load: no row >= N, no head >= H is read).
-__device__ __forceinline__ void attn_bias_rows(AttnBias& ab, const mvp_attention_bias_args& a, int h, int q0, int lane) {
+__device__ __forceinline__ void attn_bias_rows(AttnBias& ab, const mvp_attention_bias_args& a, int bh, int h, int q0, int lane) {
   const int g = lane >> 4, c16 = lane & 15;
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
     ab.row[qt] = a.bias + (size_t)h * (size_t)a.bias_head_stride + (size_t)min(q0 + qt * 16 + c16, a.att.N - 1) * (size_t)a.ld_bias + g * 4;
 }
-__device__ __forceinline__ void attn_bias_rows(AttnBias&, const mvp_attention_args&, int, int, int) {}
+// BIAS == 2: row q of pair bh of rel (no row >= N, no pair >= B * H is read).
+__device__ __forceinline__ void attn_bias_rows(AttnBias& ab, const mvp_attention_relpos_args& a, int bh, int h, int q0, int lane) {
+  const int c16 = lane & 15;
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) ab.qoff[qt] = ((unsigned)min(q0 + qt * 16 + c16, a.att.N - 1) * (unsigned)a.ld_rel) << 2;
+}
+__device__ __forceinline__ void attn_bias_rows(AttnBias&, const mvp_attention_args&, int, int, int, int) {}
+// (the pair's base is set for every wave, outside any test of the lane's rows: it must stay a wave-uniform value for the loads' scalar base)
+__device__ __forceinline__ void attn_bias_pair(AttnBias& ab, const mvp_attention_relpos_args& a, int bh) { ab.rel = a.rel + (size_t)bh * (size_t)a.rel_bh_stride; }
+__device__ __forceinline__ void attn_bias_pair(AttnBias&, const mvp_attention_bias_args&, int) {}
+__device__ __forceinline__ void attn_bias_pair(AttnBias&, const mvp_attention_args&, int) {}
+__device__ __forceinline__ void attn_bias_init(AttnBias& ab, const mvp_attention_relpos_args& a) {
+  ab.Kh = a.Kh;
+  ab.Kw = a.Kw;
+  ab.q16 = (16 / a.Kw) << 2;
+  ab.r16 = (16 % a.Kw) << 2;
+}
+__device__ __forceinline__ void attn_bias_init(AttnBias&, const mvp_attention_bias_args&) {}
+__device__ __forceinline__ void attn_bias_init(AttnBias&, const mvp_attention_args&) {}
 
-template <int SPLIT, int VF16 = 0, bool BIAS = false>
+template <int SPLIT, int VF16 = 0, int BIAS = 0>
 __global__ __launch_bounds__(256) void attention_stream_kernel(const typename AttnKArgs<BIAS>::type pa) {
   const mvp_attention_args& p = att_of(pa);
   f16_saturate_mode();
@@ -390,9 +461,11 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const typename At
   const float cs = BIAS ? 1.44269504088896340736f : p.scale * 1.44269504088896340736f;  // softmax(x*scale) via exp2 (BIAS: the tile applies scale)
   const bool active = q0 < p.N;                         // wave-uniform
   AttnBias ab{};
-  if constexpr (BIAS) {
+  if constexpr (BIAS != 0) {
     ab.scale = p.scale;
-    if (active) attn_bias_rows(ab, pa, h, q0, lane);
+    attn_bias_init(ab, pa);
+    attn_bias_pair(ab, pa, bh);
+    if (active) attn_bias_rows(ab, pa, bh, h, q0, lane);
   }
 
   auto stage = [&](int buf, int kt) {
@@ -428,7 +501,7 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const typename At
 // Per pair: [tile 0 resident, Q in registers] -> issue tiles 1.. (land under tile 0's compute) -> tile 0 -> vmcnt(0) + barrier ->
 // issue next pair's tile 0 + Q -> tiles 1.. -> vmcnt(0) (the prefetch, issued long before) -> output stores -> barrier.
 // BIAS: the bias rows follow the pair the ring is on (h = bh % H of THIS iteration), like rowbase.
-template <int SPLIT, int VF16 = 0, bool BIAS = false>
+template <int SPLIT, int VF16 = 0, int BIAS = 0>
 __global__ __launch_bounds__(512) void attention_resident_kernel(const typename AttnKArgs<BIAS>::type pa) {
   const mvp_attention_args& p = att_of(pa);
   f16_saturate_mode();
@@ -443,7 +516,10 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const typename 
   const bool active = q0 < p.N;  // wave-uniform
   const int g = lane >> 4, c16 = lane & 15;
   AttnBias ab{};
-  if constexpr (BIAS) ab.scale = p.scale;
+  if constexpr (BIAS != 0) {
+    ab.scale = p.scale;
+    attn_bias_init(ab, pa);
+  }
 
   auto stage_tile = [&](int bh, int kt, int slot) {  // 8 waves x 8 rows = one 64-key tile
     const int b = bh / p.H, h = bh - b * p.H;
@@ -476,8 +552,9 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const typename 
     const int b = bh / p.H, h = bh - b * p.H;
     const size_t rowbase = (size_t)b * p.N;
     const int s0 = (nkt * i) % nslot;  // slot of this pair's tile 0
-    if constexpr (BIAS) {
-      if (active) attn_bias_rows(ab, pa, h, q0, lane);
+    if constexpr (BIAS != 0) {
+      attn_bias_pair(ab, pa, bh);
+      if (active) attn_bias_rows(ab, pa, bh, h, q0, lane);
     }
     // this pair's remaining tiles: their slots were released at the barrier that ended the previous pair
     for (int kt = 1; kt < nkt; ++kt) stage_tile(bh, kt, (s0 + kt) % nslot);
@@ -524,7 +601,7 @@ __global__ __launch_bounds__(512) void attention_resident_kernel(const typename 
   }
 }
 
-template <int SPLIT, int VF16 = 0, bool BIAS = false>
+template <int SPLIT, int VF16 = 0, int BIAS = 0>
 int launch_attention(const typename AttnKArgs<BIAS>::type* ka, hipStream_t s) {
   const mvp_attention_args* a = &att_of(*ka);
   constexpr int NARR = (SPLIT == 3) ? 2 : 1;
@@ -572,7 +649,7 @@ static int attention_check(const mvp_attention_args* a) {
   return MVP_OK;
 }
 
-template <bool BIAS>
+template <int BIAS>
 static int attention_dispatch(const typename AttnKArgs<BIAS>::type* ka, hipStream_t s) {
   const mvp_attention_args* a = &att_of(*ka);
   if (a->precision == MVP_PREC_BF16X3) {
@@ -585,7 +662,7 @@ static int attention_dispatch(const typename AttnKArgs<BIAS>::type* ka, hipStrea
 
 extern "C" int mvp_attention_fwd(const mvp_attention_args* a, void* stream) {
   if (attention_check(a) != MVP_OK) return MVP_EINVAL;
-  return attention_dispatch<false>(a, (hipStream_t)stream);
+  return attention_dispatch<0>(a, (hipStream_t)stream);
 }
 
 extern "C" int mvp_attention_bias_fwd(const mvp_attention_bias_args* a, void* stream) {
@@ -594,5 +671,14 @@ extern "C" int mvp_attention_bias_fwd(const mvp_attention_bias_args* a, void* st
   const int64_t npad = 64 * (((int64_t)a->att.N + 63) / 64);
   if ((a->ld_bias & 3) || a->ld_bias < npad) return MVP_EINVAL;
   if (a->bias_head_stride < (int64_t)a->att.N * a->ld_bias || (a->bias_head_stride & 3)) return MVP_EINVAL;  // (every row 16-byte aligned)
-  return attention_dispatch<true>(a, (hipStream_t)stream);
+  return attention_dispatch<1>(a, (hipStream_t)stream);
+}
+
+extern "C" int mvp_attention_relpos_fwd(const mvp_attention_relpos_args* a, void* stream) {
+  if (!a || attention_check(&a->att) != MVP_OK) return MVP_EINVAL;
+  if (!a->rel || ((uintptr_t)a->rel & 3)) return MVP_EINVAL;
+  if (a->Kh <= 0 || a->Kw <= 0 || (int64_t)a->Kh * a->Kw != (int64_t)a->att.N) return MVP_EINVAL;
+  if ((int64_t)a->ld_rel < (int64_t)a->Kh + a->Kw || a->rel_bh_stride < (int64_t)a->att.N * a->ld_rel) return MVP_EINVAL;
+  if ((int64_t)a->att.N * a->ld_rel >= (1ll << 30)) return MVP_EINVAL;  // a row offset inside a pair is a 32-bit lane offset
+  return attention_dispatch<2>(a, (hipStream_t)stream);
 }

@@ -489,3 +489,33 @@ extern "C" int mvp_pack_nchw_tokens(const mvp_pack_nchw_args* a, void* stream) {
   MVP_LAUNCH_CHECK();
   return MVP_OK;
 }
+
+// Row gather of a 16-bit pair buffer (mvp_gather_rows; SAM's window partition / un-partition): out[r] = idx[r] >= 0 ? in[idx[r]] : 0.
+// One thread per 16-byte chunk of an output row; HBM-bound, no LDS, no state.  An index outside [0, rows_in) gives a zero row, so no
+// table content can make a read leave the input.
+namespace {
+__global__ __launch_bounds__(256) void gather_rows_kernel(const mvp_gather_rows_args p, const unsigned chunks, const unsigned total) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;  // (total < 2^31, host check)
+  if (i >= total) return;
+  const unsigned r = i / chunks, c = (i - r * chunks) << 3;
+  const int s = p.idx[r];
+  const bool live = s >= 0 && s < p.rows_in;
+  const size_t so = (size_t)(live ? s : 0) * p.ld_in + c, o = (size_t)r * p.ld_out + c;
+  const u32x4_t z = {0u, 0u, 0u, 0u};
+  *(u32x4_t*)(p.out_hi + o) = live ? *(const u32x4_t*)(p.in_hi + so) : z;
+  if (p.out_lo) *(u32x4_t*)(p.out_lo + o) = live ? *(const u32x4_t*)(p.in_lo + so) : z;
+}
+}  // namespace
+
+extern "C" int mvp_gather_rows(const mvp_gather_rows_args* a, void* stream) {
+  if (!a || !a->in_hi || !a->out_hi || !a->idx) return MVP_EINVAL;
+  if ((a->in_lo == nullptr) != (a->out_lo == nullptr)) return MVP_EINVAL;
+  if (a->rows <= 0 || a->rows_in <= 0 || a->cols <= 0 || (a->cols & 7)) return MVP_EINVAL;
+  if (a->ld_in < a->cols || a->ld_out < a->cols || (a->ld_in & 7) || (a->ld_out & 7)) return MVP_EINVAL;
+  if (((size_t)a->in_hi & 15) || ((size_t)a->in_lo & 15) || ((size_t)a->out_hi & 15) || ((size_t)a->out_lo & 15) || ((size_t)a->idx & 3)) return MVP_EINVAL;
+  const int64_t chunks = a->cols >> 3, total = (int64_t)a->rows * chunks;
+  if (total > 0x7fffffffll) return MVP_EINVAL;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a, (unsigned)chunks, (unsigned)total);
+  MVP_LAUNCH_CHECK();
+  return MVP_OK;
+}

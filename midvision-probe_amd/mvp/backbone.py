@@ -531,6 +531,99 @@ def random_beit_state_dict(embed_dim=768, depth=12, patch=16, img=224, seed=0, i
     return sd
 
 
+# ---------------------------------------------------------------- SAM image encoders (ViT-B / ViT-L: windowed attention, decomposed relative-position terms)
+SAM_ARCH = {"vit_b": (768, 12, 12, (2, 5, 8, 11)), "vit_l": (1024, 24, 16, (5, 11, 17, 23)), "vit_h": (1280, 32, 16, (7, 15, 23, 31))}  # arch -> (C, depth, heads, global blocks); vit_h: head dim 80, refused
+SAM_CKPT_FILES = {"vit_b": "sam_vit_b_01ec64.pth", "vit_l": "sam_vit_l_0b3195.pth", "vit_h": "sam_vit_h_4b8939.pth"}  # the published files, looked for under MVP_CKPT_DIR
+_SAM_PUB = (("norm1", "norm1"), ("norm2", "norm2"), ("attn.qkv", "attn.qkv"), ("attn.proj", "attn.proj"), ("mlp.lin1", "mlp.fc1"), ("mlp.lin2", "mlp.fc2"))
+_SAM_HF = (("layer_norm1", "norm1"), ("layer_norm2", "norm2"), ("attn.qkv", "attn.qkv"), ("attn.proj", "attn.proj"), ("mlp.lin1", "mlp.fc1"), ("mlp.lin2", "mlp.fc2"))
+
+
+def _sam_blocks(out, g, has, src_blocks, names, dst_blocks, to_engine=True):
+    i = 0
+    while has(f"{src_blocks}{i}.{(names[0][0] if to_engine else names[0][1])}.weight"):
+        sp, dp = f"{src_blocks}{i}.", f"{dst_blocks}{i}."
+        for a, b in names:
+            a, b = (a, b) if to_engine else (b, a)
+            for t in (".weight", ".bias"):
+                out[dp + b + t] = g(sp + a + t)
+        for t in ("attn.rel_pos_h", "attn.rel_pos_w"):
+            out[dp + t] = g(sp + t)
+        i += 1
+    return i
+
+
+def sam_to_engine(sd: Dict) -> Dict[str, torch.Tensor]:
+    """A SAM checkpoint -> the keys the engine reads.  Accepted: the published ``sam_vit_*.pth`` layout (``image_encoder.`` prefix or the
+    bare encoder: ``blocks.i.{norm1, attn.qkv, attn.proj, attn.rel_pos_h, attn.rel_pos_w, norm2, mlp.lin1, mlp.lin2}``, ``patch_embed.proj``,
+    ``pos_embed`` [1, S, S, C]), transformers' ``SamVisionEncoder`` layout (``vision_encoder.`` prefix or bare: ``layers.i.{layer_norm1,
+    layer_norm2, attn.*, mlp.lin1, mlp.lin2}``, ``patch_embed.projection``), and the engine's own (``mlp.fc1`` / ``mlp.fc2``; passes
+    through).  The neck (not used by the reference's forward), the prompt encoder and the mask decoder are ignored."""
+    pre = next((p for p in ("image_encoder.", "vision_encoder.", "") if p + "pos_embed" in sd), None)
+    if pre is None:
+        raise KeyError("not a SAM image-encoder state dict (pos_embed missing)")
+    g, has = (lambda k: sd[pre + k]), (lambda k: pre + k in sd)
+    out = {"pos_embed": g("pos_embed")}
+    if has("patch_embed.projection.weight"):
+        out["patch_embed.proj.weight"], out["patch_embed.proj.bias"] = g("patch_embed.projection.weight"), g("patch_embed.projection.bias")
+        n = _sam_blocks(out, g, has, "layers.", _SAM_HF, "blocks.")
+    else:
+        out["patch_embed.proj.weight"], out["patch_embed.proj.bias"] = g("patch_embed.proj.weight"), g("patch_embed.proj.bias")
+        names = _SAM_PUB if has("blocks.0.mlp.lin1.weight") else tuple((b, b) for _, b in _SAM_PUB)
+        n = _sam_blocks(out, g, has, "blocks.", names, "blocks.")
+    if n == 0:
+        raise KeyError("not a SAM image-encoder state dict (no blocks)")
+    if out["pos_embed"].dim() != 4:
+        raise KeyError(f"SAM pos_embed of shape {tuple(out['pos_embed'].shape)}: [1, S, S, C] expected")
+    return out
+
+
+def engine_to_sam_hf(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of sam_to_engine into transformers' ``SamVisionEncoder`` keys (no neck)."""
+    out = {"pos_embed": sd["pos_embed"], "patch_embed.projection.weight": sd["patch_embed.proj.weight"], "patch_embed.projection.bias": sd["patch_embed.proj.bias"]}
+    _sam_blocks(out, lambda k: sd[k], lambda k: k in sd, "blocks.", _SAM_HF, "layers.", to_engine=False)
+    return out
+
+
+def engine_to_sam(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The inverse of sam_to_engine into the published layout (``image_encoder.*``; no neck, prompt encoder or mask decoder)."""
+    out = {"pos_embed": sd["pos_embed"], "patch_embed.proj.weight": sd["patch_embed.proj.weight"], "patch_embed.proj.bias": sd["patch_embed.proj.bias"]}
+    _sam_blocks(out, lambda k: sd[k], lambda k: k in sd, "blocks.", _SAM_PUB, "blocks.", to_engine=False)
+    return {"image_encoder." + k: v for k, v in out.items()}
+
+
+def sam_block_windows(sd: Dict[str, torch.Tensor]) -> List[int]:
+    """Per block of an engine-layout SAM state dict: 0 for a global block (its tables have 2 S0 - 1 rows, S0 = the pos_embed grid's side),
+    else the window side w (2 w - 1 rows).  The checkpoint does not store global_attn_indexes: this is how they are recovered."""
+    s0 = sd["pos_embed"].shape[1]
+    out, i = [], 0
+    while f"blocks.{i}.attn.rel_pos_h" in sd:
+        side = (sd[f"blocks.{i}.attn.rel_pos_h"].shape[0] + 1) // 2
+        out.append(0 if side == s0 else side)
+        i += 1
+    return out
+
+
+def random_sam_state_dict(embed_dim=768, depth=12, native_grid=64, window=14, global_idx=(2, 5, 8, 11), seed=0, patch=16, in_chans=3) -> Dict[str, torch.Tensor]:
+    """Seeded random SAM image-encoder weights in the ENGINE's layout (used when no local checkpoint exists; ``engine_to_sam`` /
+    ``engine_to_sam_hf`` give the other two).  Blocks as random_dinov2_state_dict's (non-trivial LayerNorm affines and biases) with Q and K
+    rows large enough for peaked attention (as random_croco_state_dict), relative-position tables ~ 0.5 N(0, 1) (2 * native_grid - 1 rows
+    in the global blocks, 2 * window - 1 in the others; the reference initialises them to zero, under which a wrong index would not show),
+    a [1, S, S, C] position table ~ 0.02 N(0, 1)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {"pos_embed": 0.02 * torch.randn(1, native_grid, native_grid, embed_dim, generator=g)}
+    bound = 1.0 / math.sqrt(in_chans * patch * patch)
+    sd["patch_embed.proj.weight"] = (torch.rand(embed_dim, in_chans, patch, patch, generator=g) * 2 - 1) * bound
+    sd["patch_embed.proj.bias"] = (torch.rand(embed_dim, generator=g) * 2 - 1) * bound
+    _random_blocks(sd, "blocks.", _TIMM_BLOCK, embed_dim, depth, g)
+    for i in range(depth):
+        p = f"blocks.{i}."
+        sd[p + "attn.qkv.weight"][:2 * embed_dim] *= 1.5 / (0.02 * math.sqrt(embed_dim))
+        rows = 2 * (native_grid if i in tuple(global_idx) else window) - 1
+        sd[p + "attn.rel_pos_h"] = 0.5 * torch.randn(rows, 64, generator=g) / 8.0
+        sd[p + "attn.rel_pos_w"] = 0.5 * torch.randn(rows, 64, generator=g) / 8.0
+    return sd
+
+
 def sincos_pos_embed_2d(embed_dim: int, grid_hw, add_cls_token: bool = True) -> np.ndarray:
     """evals/models/utils.py:75-102 + HF get_2d_sincos_pos_embed_from_grid (MAE): half of the
     channels encode the w coordinate ("w goes first"), half the h coordinate; each half is

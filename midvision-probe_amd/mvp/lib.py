@@ -75,6 +75,21 @@ class AttentionBiasArgs(C.Structure):  # mvp_attention_bias_args: attention with
     _fields_ = [("att", AttentionArgs), ("bias", _vp), ("bias_head_stride", _i64), ("ld_bias", _i)]
 
 
+class GatherRowsArgs(C.Structure):  # mvp_gather_rows_args: row gather of 16-bit pair buffers by an index table (added within ABI 8)
+    _fields_ = [("in_hi", _vp), ("in_lo", _vp), ("out_hi", _vp), ("out_lo", _vp), ("idx", _vp), ("rows", _i), ("rows_in", _i), ("cols", _i),
+                ("ld_in", _i), ("ld_out", _i)]
+
+
+class RelposTermsArgs(C.Structure):  # mvp_relpos_terms_args: SAM's decomposed relative-position terms (added within ABI 8)
+    _fields_ = [("qkv", _vp), ("out_hi", _vp), ("out_lo", _vp), ("rel", _vp), ("rh", _vp), ("rw", _vp), ("rel_bh_stride", _i64),
+                ("M", _i), ("N", _i), ("H", _i), ("Qh", _i), ("Qw", _i), ("Kh", _i), ("Kw", _i), ("ld_in", _i), ("ld_out", _i), ("ld_rel", _i),
+                ("precision", _i), ("v_format", _i)]
+
+
+class AttentionRelposArgs(C.Structure):  # mvp_attention_relpos_args: attention with the decomposed bias (added within ABI 8)
+    _fields_ = [("att", AttentionArgs), ("rel", _vp), ("rel_bh_stride", _i64), ("ld_rel", _i), ("Kh", _i), ("Kw", _i)]
+
+
 class ClsRowsArgs(C.Structure):
     _fields_ = [("cls", _vp), ("pos0", _vp), ("x", _vp), ("B", _i), ("N", _i), ("C", _i)]
 
@@ -284,12 +299,17 @@ SYMBOLS = {
     "mvp_prefix_rows": PrefixRowsArgs,
     "mvp_rope2d_qkv": Rope2dQkvArgs,
     "mvp_attention_bias_fwd": AttentionBiasArgs,
+    "mvp_gather_rows": GatherRowsArgs,
+    "mvp_relpos_terms": RelposTermsArgs,
+    "mvp_attention_relpos_fwd": AttentionRelposArgs,
 }
 
 # the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
 NEW_STRUCTS_ABI7 = {"mvp_gemm_scaled_args": GemmScaledArgs, "mvp_patch_gather_ld_args": PatchGatherLdArgs, "mvp_prefix_rows_args": PrefixRowsArgs}
 
-NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs, "mvp_attention_bias_args": AttentionBiasArgs}  # the same for the additions of / within ABI 8
+NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs, "mvp_attention_bias_args": AttentionBiasArgs,
+                    "mvp_gather_rows_args": GatherRowsArgs, "mvp_relpos_terms_args": RelposTermsArgs,
+                    "mvp_attention_relpos_args": AttentionRelposArgs}  # the same for the additions of / within ABI 8
 
 _lib: Optional[C.CDLL] = None
 

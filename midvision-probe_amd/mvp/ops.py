@@ -279,14 +279,17 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out: Opt
 
 
 def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precision: int, ld_qkv=None, ld_out=None, v_f16: bool = False,
-              out_f16: bool = False, qk_f16: bool = False, bias: Optional[torch.Tensor] = None, ld_bias=None, bias_head_stride=None) -> None:
+              out_f16: bool = False, qk_f16: bool = False, bias: Optional[torch.Tensor] = None, ld_bias=None, bias_head_stride=None,
+              rel: Optional[torch.Tensor] = None, rel_grid: Optional[Tuple[int, int]] = None) -> None:
     """``v_f16``: the V third of ``qkv`` holds hi = fp16, lo = bf16 (``gemm(..., f16_col0=2 * H * 64)``); the probabilities are then held
     as one fp16 value (mvp_attention_args.v_format = MVP_ATT_V_F16; bf16x3 only).  ``out_f16``: the output pair leaves as the activation
     operand of a PREC_F16X2 GEMM (``split_f16_comp``'s form).  ``qk_f16`` (with ``v_f16``): Q and K are the compensated fp16 pairs of
     ``gemm(..., f16_col0=-2 * H * 64)`` (activation / weight-side form) and Q.K^T runs two f16 products (MVP_ATT_V_F16_QK_F16).
     ``bias``: fp32 [H, N, ld_bias] added to the logits of every image, softmax(Q K^T * scale + bias[h]) (mvp_attention_bias_fwd; natural-log
     units; ``ld_bias`` >= 64 * ceil(N / 64), default ``bias.stride(1)``; ``bias_head_stride`` default ``bias.stride(0)``; columns >= N may hold
-    anything).  None: mvp_attention_fwd, exactly as before."""
+    anything).  None: mvp_attention_fwd, exactly as before.
+    ``rel`` with ``rel_grid`` = (Kh, Kw), Kh * Kw == N: fp32 [B * H, N, ld_rel] as ``relpos_terms`` writes it; softmax(Q K^T * scale +
+    rel[bh][q][k // Kw] + rel[bh][q][Kh + k % Kw]) (mvp_attention_relpos_fwd: SAM's decomposed relative-position bias, never densified)."""
     if qk_f16 and not v_f16:
         raise lib.MvpError("attention: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
     ilv = isinstance(out, IlvPair)
@@ -295,6 +298,14 @@ def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precis
     a = lib.AttentionArgs(lib.ptr(qkv[0]), lib.ptr(qkv[1]), lib.ptr(out[0]), lib.ptr(out[1]), B, N, H,
                           ld_qkv if ld_qkv is not None else 3 * H * 64, ld_out if ld_out is not None else H * 64, scale, precision,
                           lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE, (2 if qk_f16 else 1) if v_f16 else 0, 1 if out_f16 else 0)
+    if rel is not None:
+        if bias is not None:
+            raise lib.MvpError("attention: a dense bias and decomposed relative-position terms exclude each other")
+        if rel.dtype != torch.float32 or rel.dim() != 3 or rel.stride(2) != 1 or rel_grid is None:
+            raise lib.MvpError("attention: rel must be fp32 [B * H, N, ld_rel] with unit column stride, with rel_grid=(Kh, Kw)")
+        ar = lib.AttentionRelposArgs(a, lib.ptr(rel), rel.stride(0), rel.stride(1), int(rel_grid[0]), int(rel_grid[1]))
+        _traced("attention", "4x32q relpos", precision, 4.0 * B * H * N * N * 64, lambda: lib.call("mvp_attention_relpos_fwd", ar))
+        return
     if bias is not None:
         if bias.dtype != torch.float32 or bias.dim() != 3 or bias.stride(2) != 1:
             raise lib.MvpError("attention: bias must be fp32 [H, N, ld_bias] with unit column stride")
@@ -323,6 +334,43 @@ def rope2d_qkv(qkv_f32: torch.Tensor, out: Pair, cos_tab: torch.Tensor, sin_tab:
     # algorithmic HBM bytes: the fp32 projection read once, the 16-bit pair (or single bf16) written once
     nb = M * 3 * H * 64 * (4 + (4 if out[1] is not None else 2))
     _traced("hbm", "rope2d_qkv_kernel", 0, float(nb), lambda: lib.call("mvp_rope2d_qkv", a))
+
+
+def relpos_terms(qkv_f32: torch.Tensor, out: Pair, rel: torch.Tensor, rh: torch.Tensor, rw: torch.Tensor, M: int, N: int, H: int, precision: int,
+                 v_f16: bool = False, qk_f16: bool = False, ld_in=None, ld_out=None) -> None:
+    """SAM's decomposed relative-position terms (mvp_relpos_terms): ``qkv_f32`` [M, 3 * H * 64] fp32 (``gemm(..., out_f32=...)``) ->
+    ``rel`` fp32 [M // N * H, N, ld_rel], rel[bh][q][ky] = q . rh[yq][ky], rel[bh][q][Kh + kx] = q . rw[xq][kx] on the UNSCALED q, and the
+    pair ``out`` that ``attention`` reads, every third in the form ``gemm(..., f16_col0=...)`` writes for the same ``v_f16`` / ``qk_f16``.
+    ``rh`` fp32 [Qh, Kh, 64], ``rw`` fp32 [Qw, Kw, 64], Qh * Qw == N."""
+    if qk_f16 and not v_f16:
+        raise lib.MvpError("relpos_terms: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
+    _chk(rh, torch.float32, "relpos_terms.rh")
+    _chk(rw, torch.float32, "relpos_terms.rw")
+    if qkv_f32.dtype != torch.float32 or rh.dim() != 3 or rw.dim() != 3 or rh.shape[2] != 64 or rw.shape[2] != 64:
+        raise lib.MvpError("relpos_terms: fp32 projection and fp32 [Q, K, 64] tables expected")
+    if rel.dtype != torch.float32 or rel.dim() != 3 or rel.stride(2) != 1:
+        raise lib.MvpError("relpos_terms: rel must be fp32 [B * H, N, ld_rel] with unit column stride")
+    a = lib.RelposTermsArgs(lib.ptr(qkv_f32), lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(rel), lib.ptr(rh), lib.ptr(rw), rel.stride(0), M, N, H,
+                            int(rh.shape[0]), int(rw.shape[0]), int(rh.shape[1]), int(rw.shape[1]),
+                            ld_in if ld_in is not None else 3 * H * 64, ld_out if ld_out is not None else 3 * H * 64, rel.stride(1),
+                            precision, (2 if qk_f16 else 1) if v_f16 else 0)
+    nb = M * 3 * H * 64 * (4 + (4 if out[1] is not None else 2)) + M * H * (rh.shape[1] + rw.shape[1]) * 4
+    _traced("hbm", "relpos_terms_kernel", 0, float(nb), lambda: lib.call("mvp_relpos_terms", a))
+
+
+def gather_rows(src, dst, idx: torch.Tensor, rows_in: int, cols: int, ld_in=None, ld_out=None) -> None:
+    """dst[r] = src[idx[r]] if idx[r] >= 0 else 0 for r < len(idx) (mvp_gather_rows): a bit copy of ``cols`` 16-bit elements per row of a
+    pair (hi, lo) — lo may be None on both sides — or of an ``IlvPair`` (then ``cols`` counts the pair's columns; both sides interleaved)."""
+    if isinstance(src, IlvPair) != isinstance(dst, IlvPair):
+        raise lib.MvpError("gather_rows: source and destination must have the same pair form")
+    if isinstance(src, IlvPair):
+        src, dst, cols = (src.t, None), (dst.t, None), 2 * cols
+    if idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise lib.MvpError("gather_rows: idx must be a contiguous int32 tensor")
+    a = lib.GatherRowsArgs(lib.ptr(src[0]), lib.ptr(src[1]), lib.ptr(dst[0]), lib.ptr(dst[1]), lib.ptr(idx), int(idx.numel()), int(rows_in), int(cols),
+                           ld_in if ld_in is not None else cols, ld_out if ld_out is not None else cols)
+    nb = idx.numel() * cols * 2 * (2 if src[1] is not None else 1) * 2
+    _traced("hbm", "gather_rows_kernel", 0, float(nb), lambda: lib.call("mvp_gather_rows", a))
 
 
 def cls_rows(cls: torch.Tensor, pos0: torch.Tensor, x: torch.Tensor, B: int, N: int, Cdim: int) -> None:

@@ -182,6 +182,46 @@ def dense_rel_pos_bias(table: torch.Tensor, gh: int, gw: int, ld: Optional[int] 
     return out
 
 
+def check_head_dim(C: int, heads: int) -> None:
+    if C != heads * 64:
+        raise lib.MvpError(f"attention kernel requires head_dim 64 (C={C}, heads={heads})")
+
+
+def sam_rel_pos(q_size: int, k_size: int, rel_pos: torch.Tensor) -> torch.Tensor:
+    """segment_anything's ``get_rel_pos`` (image_encoder.py; transformers' SamVisionAttention.get_rel_pos is the same code) followed by the
+    gather: a table [L, 64] -> fp32 [q_size, k_size, 64], R[q][k] = the table row of the relative position of query coordinate q and key
+    coordinate k.  On the CPU in fp32 with the reference's own torch expressions: linear ``F.interpolate`` to 2 * max(q, k) - 1 rows when
+    the length differs, then the coordinate index with its q / k scale factors."""
+    rel_pos = rel_pos.detach().to("cpu", torch.float32)
+    max_rel_dist = int(2 * max(q_size, k_size) - 1)
+    if rel_pos.shape[0] != max_rel_dist:
+        r = F.interpolate(rel_pos.reshape(1, rel_pos.shape[0], -1).permute(0, 2, 1), size=max_rel_dist, mode="linear")
+        r = r.reshape(-1, max_rel_dist).permute(1, 0)
+    else:
+        r = rel_pos
+    q_coords = torch.arange(q_size)[:, None] * max(k_size / q_size, 1.0)
+    k_coords = torch.arange(k_size)[None, :] * max(q_size / k_size, 1.0)
+    relative_coords = (q_coords - k_coords) + (k_size - 1) * max(q_size / k_size, 1.0)
+    return r[relative_coords.long()].contiguous()
+
+
+def sam_window_index(B: int, gh: int, gw: int, w: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The row tables of SAM's window partition for B images of a gh x gw grid and w x w windows (segment_anything's window_partition /
+    window_unpartition as row gathers, mvp_gather_rows), int32 on the CPU: ``part`` [B * nW * w * w] — row ((b * nWh + wy) * nWw + wx) * w * w
+    + iy * w + ix of the window-major order takes token row b * gh * gw + y * gw + x with (y, x) = (wy * w + iy, wx * w + ix), or -1 (a
+    zero row) where the zero-padded grid (gh, gw rounded up to multiples of w) lies outside the image; ``unpart`` [B * gh * gw] — its inverse
+    on the real rows."""
+    nwh, nww = -(-gh // w), -(-gw // w)
+    y = (torch.arange(nwh)[:, None, None, None] * w + torch.arange(w)[None, None, :, None]).expand(nwh, nww, w, w)
+    x = (torch.arange(nww)[None, :, None, None] * w + torch.arange(w)[None, None, None, :]).expand(nwh, nww, w, w)
+    one = torch.where((y < gh) & (x < gw), y * gw + x, torch.full_like(y, -1)).reshape(-1)  # one image, window-major
+    part = torch.where(one[None, :] >= 0, one[None, :] + torch.arange(B)[:, None] * (gh * gw), torch.full((1, 1), -1, dtype=torch.int64)).reshape(-1)
+    unpart = torch.empty(B * gh * gw, dtype=torch.int64)
+    live = part >= 0
+    unpart[part[live]] = torch.arange(part.numel())[live]
+    return part.to(torch.int32).contiguous(), unpart.to(torch.int32).contiguous()
+
+
 class ViTEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, heads: int, patch: int = 16, ln_eps: float = 1e-6,
                  precision="bf16x3", device="cuda", pos_embed_mode: str = "dino", qkv_fused: bool = True, act: str = "gelu",
@@ -204,7 +244,10 @@ class ViTEngine:
         the CPU in fp32, into the dense [H, N, ld] array that attention adds to its logits (``dense_rel_pos_bias``; blocks with identical
         tables share one array).  Such a model may have a class token and no ``pos_embed`` (the class row is ``cls_token`` alone, the patch
         rows get no position residual), and a forward at another grid raises.  ``fc_norm.weight`` / ``fc_norm.bias`` (BEiT's final norm)
-        are kept for ``forward_taps(..., replay_after_norm=True)``."""
+        are kept for ``forward_taps(..., replay_after_norm=True)``.
+        SAM's image encoder is picked up from ``blocks.i.attn.rel_pos_h`` / ``rel_pos_w`` [2S - 1, 64] (with pos_embed_mode='sam' and a
+        [1, S0, S0, C] ``pos_embed``): a block whose S equals S0 attends globally, any other inside S x S windows of the zero-padded grid
+        (``_sam_attention``).  No class token, no prefix rows."""
         self.device = torch.device(device)
         self.precision = parse_precision(precision)
         # 'f16x2': a bf16x3 engine (buffers, patch embedding, attention, taps) whose four block GEMMs run two products (lib.PREC_F16X2)
@@ -232,8 +275,7 @@ class ViTEngine:
             raise lib.MvpError("state dict without pos_embed: only a RoPE model without a class token (rope_freq=...) or a model with "
                                "relative-position bias tables (rel_pos_grid=...) has none")
         self.C = sd["cls_token"].shape[-1] if self.has_cls else sd["pos_embed"].shape[-1] if "pos_embed" in sd else sd["patch_embed.proj.weight"].shape[0]
-        if self.C != heads * 64:
-            raise lib.MvpError(f"attention kernel requires head_dim 64 (C={self.C}, heads={heads})")
+        check_head_dim(self.C, heads)
         self.depth = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("blocks."))
         self.cls = sd["cls_token"].reshape(-1).contiguous() if self.has_cls else None
         self.pos_embed = sd.get("pos_embed")  # [1, 1+n, C] fp32 ([1, n, C] without a CLS token); None: a RoPE model without a table
@@ -255,6 +297,15 @@ class ViTEngine:
             pw2 = F.pad(pw2, (0, self.k_patch - kp)).contiguous()
         self.w_patch = ops.split_bf16(pw2, self.precision)
         self.b_patch = sd.get("patch_embed.proj.bias")  # (CLIP's patch convolution has none)
+        self.sam = "blocks.0.attn.rel_pos_h" in sd
+        if self.sam and (self.pos_embed is None or self.pos_embed.dim() != 4 or self.pos_embed.shape[1] != self.pos_embed.shape[2]
+                         or self.has_cls or pos_embed_mode != "sam" or self.rope_freq is not None or self.rel_pos_grid is not None):
+            raise lib.MvpError("decomposed relative-position tables (blocks.i.attn.rel_pos_h): a SAM encoder has a square [1, S, S, C] pos_embed, "
+                               "no class token and pos_embed_mode='sam'")
+        self._pos_cpu = state_dict["pos_embed"].detach().to("cpu", torch.float32) if self.sam else None  # the checkpoint's table: every size resamples THIS
+        self._sam_tables: List[Tuple[torch.Tensor, torch.Tensor]] = []  # distinct (rel_pos_h, rel_pos_w) on the CPU
+        self._sam_rel: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}  # (table id, Kh, Kw) -> (Rh, Rw) on the device
+        self._sam_win: Dict[Tuple[int, int, int, int], Tuple[torch.Tensor, torch.Tensor, int]] = {}  # (B, gh, gw, w) -> (part, unpart, windows)
         self.blocks = []
         self._bias_tables: List[Tuple[torch.Tensor, torch.Tensor]] = []  # (table on the CPU, its dense [H, N, ld] bias on the device)
         for i in range(self.depth):
@@ -277,6 +328,15 @@ class ViTEngine:
                     blk[n + "_ilv"] = ops.interleave_pair(blk[n])
             if self.rel_pos_grid is not None:
                 blk["att_bias"] = self._dense_bias(state_dict[p + "attn.rel_pos_bias_table"])
+            if self.sam:
+                th, tw = (state_dict[p + "attn.rel_pos_" + a].detach().to("cpu", torch.float32) for a in "hw")
+                if th.dim() != 2 or th.shape != tw.shape or th.shape[1] != 64 or th.shape[0] % 2 == 0:
+                    raise lib.MvpError(f"block {i}: rel_pos_h / rel_pos_w of {tuple(th.shape)} / {tuple(tw.shape)}: two [2S - 1, 64] tables expected")
+                side = (th.shape[0] + 1) // 2
+                blk["window"] = 0 if side == self.pos_embed.shape[1] else side  # 0: global attention
+                blk["sam_tid"] = next((j for j, (a, b) in enumerate(self._sam_tables) if torch.equal(a, th) and torch.equal(b, tw)), len(self._sam_tables))
+                if blk["sam_tid"] == len(self._sam_tables):
+                    self._sam_tables.append((th, tw))
             self.blocks.append(blk)
         self.fc_norm = (sd["fc_norm.weight"], sd["fc_norm.bias"]) if "fc_norm.weight" in sd else None  # BEiT's final norm (replay_after_norm)
         self._zero_c = torch.zeros(self.C, dtype=torch.float32, device=self.device) if self.pos_embed is None and self.has_cls else None
@@ -310,19 +370,34 @@ class ViTEngine:
             # operands — LayerNorm output, attention output, fc1 output — are kept as hi|lo-interleaved arrays (ops.IlvPair): a 32-deep
             # k-step of a row is then one whole 128-byte line for the LDS-DMA (2-3 % per GEMM on top of the interleaved weights).
             gp = lib.PREC_F16X2 if self.f16x2 else pr  # precision of the four block GEMMs
+            # SAM: the qkv GEMM of a windowed block runs over the padded row count Mp of its windows, so that shape must go there as well
+            Mp, nrel, windowed = M, 0, False
+            if self.sam:  # the padded row count of the windowed blocks and the longest rel buffer of any block
+                for w in {b["window"] for b in self.blocks}:
+                    Bp, Np, K = (B * -(-gh // w) * -(-gw // w), w * w, 2 * w) if w else (B, N, gh + gw)
+                    Mp, nrel, windowed = max(Mp, Bp * Np), max(nrel, Bp * self.heads * Np * (-(-K // 4) * 4)), windowed or w > 0
+            shapes = [(M, 3 * C, C), (M, C, C), (M, self.hidden, C), (M, C, self.hidden)] + ([(Mp, 3 * C, C)] if windowed else [])
             ilv = (pr == PREC_BF16X3 and os.environ.get("MVP_ILV", "1") != "0" and C % 32 == 0 and self.hidden % 32 == 0 and
-                   all(ops.gemm_tile(M, n, k, gp, 1, pipeline.tile_policy()).startswith("pp ") for n, k in ((3 * C, C), (C, C), (self.hidden, C), (C, self.hidden))))
+                   all(ops.gemm_tile(m, n, k, gp, 1, pipeline.tile_policy()).startswith("pp ") for m, n, k in shapes))
+            a_pair = lambda rows, cols: ops.IlvPair(rows, cols, dev) if ilv else ops.empty_pair((rows, cols), pr, dev)
             xfull = torch.empty(M + headroom * N, C, dtype=torch.float32, device=dev)
             # RoPE engines only: the fp32 projection that mvp_rope2d_qkv reads, and the grid its positions come from
             rope = dict(qkv_f32=torch.empty(M, 3 * C, dtype=torch.float32, device=dev), grid=(gh, gw)) if self.rope_freq is not None else {}
+            sam = {}
+            if self.sam:
+                sam = dict(grid=(gh, gw), qkv_f32=torch.empty(Mp, 3 * C, dtype=torch.float32, device=dev), rel=torch.empty(nrel, dtype=torch.float32, device=dev),
+                           qkv=ops.empty_pair((Mp, 3 * C), pr, dev))
+                if windowed:  # LayerNorm 1's output and the attention output in window order (A operands like xn and ao)
+                    sam.update(xw=a_pair(Mp, C), aow=a_pair(Mp, C))
             return dict(
                 **rope,
                 xfull=xfull, headroom=headroom, x=xfull[headroom * N:],
-                xn=ops.IlvPair(M, C, dev) if ilv else ops.empty_pair((M, C), pr, dev),
-                qkv=ops.empty_pair((M, 3 * C), pr, dev),
-                ao=ops.IlvPair(M, C, dev) if ilv else ops.empty_pair((M, C), pr, dev),
-                hmid=ops.IlvPair(M, self.hidden, dev) if ilv else ops.empty_pair((M, self.hidden), pr, dev),
+                xn=a_pair(M, C),
+                qkv=sam["qkv"] if self.sam else ops.empty_pair((M, 3 * C), pr, dev),
+                ao=a_pair(M, C),
+                hmid=a_pair(M, self.hidden),
                 patches=ops.empty_pair((B * gh * gw, self.k_patch), pr, dev),
+                **{k: v for k, v in sam.items() if k != "qkv"},
             )
 
         return self._buffers.workspace((B, gh, gw), headroom, alloc)
@@ -333,7 +408,30 @@ class ViTEngine:
         pipeline keeps this list alive with the graph, because the engine itself drops the buffers of other resolutions when a new one
         arrives."""
         return (self._buffers.snapshot(slot) + list(self._pos.values()) + [t for cs in self._rope.values() for t in cs] +
-                [dense for _, dense in self._bias_tables])
+                [dense for _, dense in self._bias_tables] + [t for rs in self._sam_rel.values() for t in rs] +
+                [t for pu in self._sam_win.values() for t in pu[:2]])
+
+    def sam_rel_tables(self, i: int, kh: int, kw: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(Rh [kh, kh, 64], Rw [kw, kw, 64]) of block i for a kh x kw query = key grid, on the device (``sam_rel_pos`` of the block's
+        tables); cached per grid and per distinct table pair beside the position tables."""
+        key = (self.blocks[i]["sam_tid"], kh, kw)
+        rs = self._sam_rel.get(key)
+        if rs is None:
+            th, tw = self._sam_tables[key[0]]
+            rs = self._sam_rel[key] = (sam_rel_pos(kh, kh, th).to(self.device), sam_rel_pos(kw, kw, tw).to(self.device))
+            pipeline.publish()
+        return rs
+
+    def sam_windows(self, B: int, gh: int, gw: int, w: int) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """(partition table, un-partition table, number of windows) of B images at gh x gw with w x w windows, on the device
+        (``sam_window_index``); built once per (B, gh, gw, w)."""
+        key = (B, gh, gw, w)
+        pu = self._sam_win.get(key)
+        if pu is None:
+            part, unpart = sam_window_index(B, gh, gw, w)
+            pu = self._sam_win[key] = (part.to(self.device), unpart.to(self.device), B * -(-gh // w) * -(-gw // w))
+            pipeline.publish()
+        return pu
 
     def rope_for(self, gh: int, gw: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The cos / sin tables of RoPE<rope_freq> for a gh x gw grid, fp32 [max(gh, gw), 32], row = grid coordinate: the reference's
@@ -359,6 +457,13 @@ class ViTEngine:
         key = (gh, gw)
         pe = self._pos.get(key)
         if pe is not None:
+            return pe
+        if self.pos_embed_mode == "sam":  # plain bicubic resample of the CHECKPOINT's [1, S, S, C] table (sam.py:70-83), on the CPU in fp32
+            t = self._pos_cpu
+            if (gh, gw) != tuple(t.shape[1:3]):
+                t = F.interpolate(t.permute(0, 3, 1, 2), size=(gh, gw), mode="bicubic").permute(0, 2, 3, 1)
+            pe = self._pos[key] = t.reshape(gh * gw, self.C).contiguous().to(self.device)
+            pipeline.publish()
             return pe
         c0 = 1 if self.has_cls else 0  # the table's CLS entry
         n = self.pos_embed.shape[1] - c0
@@ -421,6 +526,12 @@ class ViTEngine:
                  precision=self.precision, row_group=gh * gw, row_group_stride=N, row_group_off=npre, res_row_mod=gh * gw if pos is not None else 0)
         if self.rope_freq is not None:
             self.rope_for(gh, gw)  # (built and published here, before any block runs)
+        if self.sam:  # index tables and relative-position tables of every block, likewise
+            for i, blk in enumerate(self.blocks):
+                w = blk["window"]
+                if w:
+                    self.sam_windows(B, gh, gw, w)
+                self.sam_rel_tables(i, w or gh, w or gw)
         if not self.has_cls:
             pass  # no prefix rows at all (SigLIP)
         elif self.reg is None:
@@ -452,6 +563,32 @@ class ViTEngine:
                  precision=lib.PREC_F16X2 if f2 else self.precision, w_ilv=blk.get("qkv_w_ilv"),
                  f16_col0=(-2 * C if self.att_qk_f16 else 2 * C) if (pairs and self.att_v_f16) else 0)
 
+    def _sam_attention(self, i: int, ws: dict, B: int, N: int) -> None:
+        """LayerNorm 1 up to the attention output ws['ao'] of a SAM block.  Windowed block: LN1, gather into windows (pad rows zero AFTER the
+        norm, so they pass the qkv GEMM and are real keys with k = b_k, v = b_v, as in segment_anything), qkv GEMM over the B * nW * w^2
+        padded rows as fp32, relative-position terms + conversion (mvp_relpos_terms), attention per window with the decomposed bias, gather
+        back (pad rows dropped).  Global block: no gathers, one "window" per image of the whole gh x gw grid."""
+        blk, C, M, pr, f2 = self.blocks[i], self.C, B * N, self.precision, self.f16x2
+        gh, gw = ws["grid"]
+        w = blk["window"]
+        ops.layernorm(ws["x"], blk["n1w"], blk["n1b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
+        if w:
+            part, unpart, Bp = self.sam_windows(B, gh, gw, w)
+            Np, kh, kw = w * w, w, w
+            ops.gather_rows(ws["xn"], ws["xw"], part, M, C)
+            a_in, ao = ws["xw"], ws["aow"]
+        else:
+            Bp, Np, kh, kw, a_in, ao = B, N, gh, gw, ws["xn"], ws["ao"]
+        Mp = Bp * Np
+        ops.gemm(a_in, blk["qkv_w"], Mp, 3 * C, C, bias=blk["qkv_b"], out_f32=ws["qkv_f32"], precision=lib.PREC_F16X2 if f2 else pr, w_ilv=blk.get("qkv_w_ilv"))
+        rh, rw = self.sam_rel_tables(i, kh, kw)
+        ld = -(-(kh + kw) // 4) * 4
+        rel = ws["rel"][:Bp * self.heads * Np * ld].view(Bp * self.heads, Np, ld)
+        ops.relpos_terms(ws["qkv_f32"], ws["qkv"], rel, rh, rw, Mp, Np, self.heads, pr, v_f16=self.att_v_f16, qk_f16=self.att_qk_f16)
+        ops.attention(ws["qkv"], ao, Bp, Np, self.heads, 64 ** -0.5, pr, v_f16=self.att_v_f16, qk_f16=self.att_qk_f16, out_f16=f2, rel=rel, rel_grid=(kh, kw))
+        if w:
+            ops.gather_rows(ws["aow"], ws["ao"], unpart, Mp, C)
+
     def run_block(self, i: int, ws: dict, B: int, N: int) -> None:
         blk, C, M, pr = self.blocks[i], self.C, B * N, self.precision
         f2 = self.f16x2
@@ -459,7 +596,9 @@ class ViTEngine:
         gp = lib.PREC_F16X2 if f2 else pr  # precision of the four block GEMMs
         x = ws["x"]
         vf16, qk16 = self.att_v_f16, self.att_qk_f16
-        if self.rope_freq is None:
+        if self.sam:
+            self._sam_attention(i, ws, B, N)
+        elif self.rope_freq is None:
             self._ln1_qkv(i, ws, M)
         else:  # the projection as fp32, then rotation + conversion into the forms the attention kernel reads (mvp_rope2d_qkv)
             gh, gw = ws["grid"]
@@ -470,7 +609,8 @@ class ViTEngine:
             self._check_f16_range(f"block {i}: LayerNorm 1 output", ws["xn"], M)
         if chk and qk16:
             self._check_f16_range(f"block {i}: Q / K", (ws["qkv"][0][:, :2 * C], ws["qkv"][1][:, :2 * C]), M)
-        ops.attention(ws["qkv"], ws["ao"], B, N, self.heads, 64 ** -0.5, pr, v_f16=vf16, qk_f16=qk16, out_f16=f2, bias=blk.get("att_bias"))
+        if not self.sam:
+            ops.attention(ws["qkv"], ws["ao"], B, N, self.heads, 64 ** -0.5, pr, v_f16=vf16, qk_f16=qk16, out_f16=f2, bias=blk.get("att_bias"))
         if chk:
             self._check_f16_range(f"block {i}: attention output", ws["ao"], M)
         ops.gemm(ws["ao"], blk["proj_w"], M, C, C, bias=blk["proj_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("proj_w_ilv"),

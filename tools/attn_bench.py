@@ -2,6 +2,8 @@
 """Attention microbenchmark + ablation (diagnostic).  Builds ablated copies of attention.hip under
 gpurun_out/ and times the hot-path shape with HIP events, interleaved rounds in one process.
 ablate: 0 full, 1 no softmax VALU, 2 no PV MFMAs, 3 no S MFMAs, 4 no K/V staging, 5 no tiles (prologue+epilogue).
+--relpos: instead, mvp_attention_relpos_fwd (SAM's decomposed relative-position bias) against mvp_attention_fwd, plus mvp_relpos_terms and
+the two row gathers of a windowed block (relpos_ab).
 --bias: instead, the shipped library's mvp_attention_bias_fwd (a dense fp32 [H, N, ld] logit bias) against mvp_attention_fwd on the same
 operands, alternating, at N = 197 and 577 (env N="197 577"), B from env B (default 110), H = 12, every bf16x3 operand form."""
 import ctypes as C, os, subprocess, sys
@@ -63,9 +65,63 @@ def bias_ab():
                   f"bias array {H * N * ld * 4 / 1e6:.2f} MB", flush=True)
 
 
+def relpos_ab():
+    """mvp_attention_relpos_fwd against mvp_attention_fwd at the same (B', N, H) (N = K * K keys on a K x K grid), the cost of
+    mvp_relpos_terms and of the two row gathers of a windowed block: three alternations of 20 launches each, median per variant.
+    Environment: B (images, default 4), N (default "196 4096"; N = 196 runs B' = 25 B windows, the 1024^2 geometry), H (default 12)."""
+    import statistics
+    dev = torch.device("cuda")
+    B = int(os.environ.get("B", 4)); H = int(os.environ.get("H", 12)); Cw = H * 64
+    so = lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / 20 * 1e3
+
+    for N in (int(n) for n in os.environ.get("N", "196 4096").split()):
+        K = int(round(N ** 0.5))
+        assert K * K == N
+        Bp = 25 * B if N == 196 else B
+        M, ld = Bp * N, -(-2 * K // 4) * 4
+        qf = torch.randn(M, 3 * Cw, device=dev) * 0.5
+        rh, rw = torch.randn(K, K, 64, device=dev) * 0.1, torch.randn(K, K, 64, device=dev) * 0.1
+        rel = torch.empty(Bp * H, N, ld, device=dev)
+        qkv, out = ops.empty_pair((M, 3 * Cw), 3, dev), ops.empty_pair((M, Cw), 3, dev)
+        res = {}
+        for vf, form in ((2, "bf16x3_vf16_qk16"), (1, "bf16x3_vf16"), (0, "bf16x3")):
+            terms = lambda: ops.relpos_terms(qf, qkv, rel, rh, rw, M, N, H, 3, v_f16=vf > 0, qk_f16=vf == 2)
+            terms()
+            att = lib.AttentionArgs(qkv[0].data_ptr(), qkv[1].data_ptr(), out[0].data_ptr(), out[1].data_ptr(), Bp, N, H, 3 * Cw, Cw, 0.125, 3, 0, vf, 0)
+            ar = lib.AttentionRelposArgs(att, rel.data_ptr(), N * ld, ld, K, K)
+            calls = {"plain": lambda: so.mvp_attention_fwd(C.byref(att), st), "relpos": lambda: so.mvp_attention_relpos_fwd(C.byref(ar), st), "terms": terms}
+            res = {k: [] for k in calls}
+            for rnd in range(3):
+                for vn, fn in calls.items():
+                    res[vn].append(timed(fn))
+            mp, mr, mt = (statistics.median(res[k]) for k in ("plain", "relpos", "terms"))
+            print(f"B'={Bp} N={N} ({K}x{K}) H={H} {form}: plain {mp:8.1f} us  relpos {mr:8.1f} us  relpos / plain = {mr / mp:.3f}  "
+                  f"relpos_terms {mt:7.1f} us  rel {Bp * H * N * ld * 4 / 1e6:.1f} MB", flush=True)
+        if N == 196:  # the two gathers of a windowed block at 1024^2: 64 x 64 grid, 25 windows of 14 x 14 per image
+            from mvp import vit
+            part, unpart = (t.to(dev) for t in vit.sam_window_index(B, 64, 64, 14))
+            xn, xw = ops.empty_pair((B * 4096, Cw), 3, dev), ops.empty_pair((M, Cw), 3, dev)
+            gp = statistics.median(timed(lambda: ops.gather_rows(xn, xw, part, B * 4096, Cw)) for _ in range(3))
+            gu = statistics.median(timed(lambda: ops.gather_rows(xw, xn, unpart, M, Cw)) for _ in range(3))
+            print(f"B={B} 64x64 grid, w=14: gather into windows {gp:.1f} us, gather back {gu:.1f} us", flush=True)
+
+
 def main():
     if "--bias" in sys.argv:
         return bias_ab()
+    if "--relpos" in sys.argv:
+        return relpos_ab()
     names = {0: "full", 1: "no_softmax", 2: "no_pv", 3: "no_s", 4: "no_stage", 5: "no_tiles"}
     variants = {names[a]: build(a) for a in names}
     prev = os.path.join(REPO, "tools", "micro", "attention_prev.hip")

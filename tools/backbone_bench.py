@@ -28,7 +28,10 @@ MODELS = {"dino_b16": ("dino", "vitb16", "dense"), "dinov2_b14": ("dinov2", "vit
           # the same GEMMs; crocov2 adds mvp_rope2d_qkv and the fp32 qkv output per block
           "croco_b16": ("croco", "vitb16", "dense"), "crocov2_b16": ("crocov2", "vitb16", "dense"),
           # 24 block passes per forward (all blocks + fc_norm, then the tapped pass) with a logit bias in attention
-          "beit-v2_vitb16": ("beit_v2", "vitb16", "dense")}
+          "beit-v2_vitb16": ("beit_v2", "vitb16", "dense"),
+          # windowed blocks: two row gathers, fp32 qkv + mvp_relpos_terms, attention with the decomposed bias (SAM); no tap norm
+          # (the wrapper refuses add_norm); --size 512 / 1024 for the sizes the encoder is meant for
+          "sam_base": ("sam", "vit_b", "dense"), "sam_large": ("sam", "vit_l", "dense")}
 
 
 def build(name, precision, dev):
@@ -45,6 +48,10 @@ def build(name, precision, dev):
             from evals.models.crocov2 import CROCOV2
 
             model = (CROCO if dn == "croco" else CROCOV2)(model_name=mn, output=out, return_multilayer=True, add_norm=True, precision=precision).to(dev)
+        elif dn == "sam":
+            from evals.models.sam import SAM
+
+            model = SAM(mn, output=out, return_multilayer=True, precision=precision).to(dev)
         elif dn == "beit_v2":
             from evals.models.beit_v2 import BEiTV2
 
@@ -70,9 +77,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--precision", default="f16x2")
     ap.add_argument("--models", default=",".join(MODELS))
+    ap.add_argument("--size", type=int, default=224, help="image side (a multiple of every patch size used: 224, 448, ...; SAM: 512, 1024)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    B, H, W = a.batch, 224, 224
+    B, H, W = a.batch, a.size, a.size
     names = a.models.split(",")
     batches = []
     for s in range(4):
