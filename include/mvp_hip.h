@@ -80,6 +80,8 @@ typedef struct {
                                 Added within 8: mvp_gather_rows (row gather of 16-bit pair buffers by an index table), mvp_relpos_terms (SAM's
                                 decomposed relative-position terms of the unscaled q) and mvp_attention_relpos_fwd (attention with that decomposed
                                 bias); three new exports, each with its own tagged argument struct, no existing struct changed.
+                                Added within 8: mvp_knn_ratio and mvp_knn_workspace_bytes (top-2 cosine nearest neighbours with the ratio test,
+                                NAVI / ScanNet 3-D correspondence); a new export with its own tagged argument struct, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -636,6 +638,40 @@ typedef struct {
   const float* x; int64_t* out_xy; int K, h, w, max_value;
 } mvp_argmax_2d_args;
 int mvp_argmax_2d(const mvp_argmax_2d_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)
+ * Top-2 cosine nearest neighbours with the ratio test: the hot loop of the NAVI / ScanNet 3-D correspondence evaluation
+ * (evals/utils/correspondence.py:26-121, where faiss does the search).  Definition, per query i with src_valid[i] != 0:
+ *     q^ = q / max(|q|, 1e-12),  t^_j likewise (F.normalize),  d(i, j) = 1 - <q^_i, t^_j>   over the targets with tgt_valid[j] != 0
+ *     nn_idx[i] = argmin_j d(i, j)  (GRID index j, lowest j among ties),  dist[i] = the two smallest d, ascending
+ *     weight[i] = 1 - max(dist[i][0], 1e-9) / max(dist[i][1], 1e-9)          (calculate_ratio_test, both clamps)
+ * An invalid query, and every query when fewer than two targets are valid, gets nn_idx = -1, weight = -inf, dist = +inf.
+ * n_valid = {number of valid queries, number of valid targets}.
+ * How: both views are normalised and packed once (fp32 rows for the exact step, compensated fp16 pairs of MVP_PREC_F16X2 for the
+ * matrix pipe, C zero-padded to a multiple of 32); an MFMA kernel keeps, per query, the best 4 targets of each slice of the target
+ * range in registers (the N0 x N1 score matrix is never written); a last kernel merges the slices, recomputes the 4 survivors'
+ * distances in fp32 from the fp32 rows and orders them.  Every merge orders by (score, index), so the result does not depend on
+ * the slicing and two calls give the same bits.  No atomics, no sync, no allocation.
+ * MVP_EINVAL: a NULL pointer other than src_valid / tgt_valid, C <= 0 or C > 16384, N0 <= 0, N1 < 2, N0 or N1 > 2^24,
+ * workspace_bytes < mvp_knn_workspace_bytes(C, N0, N1), a workspace that is not 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_knn_ratio_args mvp_knn_ratio_args;
+struct mvp_knn_ratio_args {
+  const float* src_feat; const float* tgt_feat;       /* fp32, channel-major [C, N0] / [C, N1] (a [C, h, w] map, flattened)   */
+  const uint8_t* src_valid; const uint8_t* tgt_valid; /* optional [N0] / [N1], non-zero = valid; NULL = all valid             */
+  int32_t* nn_idx;                                    /* [N0]   index into the target grid, -1 for an invalid query           */
+  float* dist;                                        /* [N0,2] the two smallest cosine distances, ascending                  */
+  float* weight;                                      /* [N0]   ratio-test weight, -inf for an invalid query                  */
+  int32_t* n_valid;                                   /* [2]    device counts of valid queries / targets                      */
+  void* workspace; int64_t workspace_bytes;           /* >= mvp_knn_workspace_bytes(C, N0, N1), 16-byte aligned               */
+  int C, N0, N1;
+};
+/* Workspace: (N0 + N1) * Cpad * 8 + S * N0 * 32 bytes, Cpad = C rounded up to 32 (fp32 rows and the fp16 pair of both views, then 4
+ * candidates of 8 bytes per query and target slice); S = ceil(T / ceil(T / min(T, ceil(512 / ceil(N0 / 128))))) slices of the
+ * T = ceil(N1 / 128) target tiles.  0 for sizes that mvp_knn_ratio rejects. */
+int64_t mvp_knn_workspace_bytes(int C, int N0, int N1);
+int mvp_knn_ratio(const mvp_knn_ratio_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution weight re-layout (per step; the probe's conv weights are trained):

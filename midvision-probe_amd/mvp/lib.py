@@ -173,6 +173,11 @@ class Argmax2dArgs(C.Structure):
     _fields_ = [("x", _vp), ("out_xy", _vp), ("K", _i), ("h", _i), ("w", _i), ("max_value", _i)]
 
 
+class KnnRatioArgs(C.Structure):  # mvp_knn_ratio_args: top-2 cosine nearest neighbours + ratio test (added within ABI 8)
+    _fields_ = [("src_feat", _vp), ("tgt_feat", _vp), ("src_valid", _vp), ("tgt_valid", _vp), ("nn_idx", _vp), ("dist", _vp), ("weight", _vp),
+                ("n_valid", _vp), ("workspace", _vp), ("workspace_bytes", _i64), ("C", _i), ("N0", _i), ("N1", _i)]
+
+
 class ScaleShiftArgs(C.Structure):
     _fields_ = [("x", _vp), ("scale_shift", _vp), ("grad_out", _vp), ("out", _vp), ("B", _i), ("HW", _i64), ("lo", _f), ("hi", _f),
                 ("clamp", _i), ("backward", _i)]
@@ -302,6 +307,8 @@ SYMBOLS = {
     "mvp_gather_rows": GatherRowsArgs,
     "mvp_relpos_terms": RelposTermsArgs,
     "mvp_attention_relpos_fwd": AttentionRelposArgs,
+    "mvp_knn_ratio": KnnRatioArgs,
+    "mvp_knn_workspace_bytes": None,
 }
 
 # the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
@@ -309,7 +316,7 @@ NEW_STRUCTS_ABI7 = {"mvp_gemm_scaled_args": GemmScaledArgs, "mvp_patch_gather_ld
 
 NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs, "mvp_attention_bias_args": AttentionBiasArgs,
                     "mvp_gather_rows_args": GatherRowsArgs, "mvp_relpos_terms_args": RelposTermsArgs,
-                    "mvp_attention_relpos_args": AttentionRelposArgs}  # the same for the additions of / within ABI 8
+                    "mvp_attention_relpos_args": AttentionRelposArgs, "mvp_knn_ratio_args": KnnRatioArgs}  # the same for the additions of / within ABI 8
 
 _lib: Optional[C.CDLL] = None
 
@@ -338,6 +345,8 @@ def load() -> C.CDLL:
     lib.mvp_strerror.restype = C.c_char_p
     lib.mvp_corr_workspace_bytes.argtypes = [_i, _i, _i, _i]
     lib.mvp_corr_workspace_bytes.restype = _i64
+    lib.mvp_knn_workspace_bytes.argtypes = [_i, _i, _i]
+    lib.mvp_knn_workspace_bytes.restype = _i64
     lib.mvp_sizeof.argtypes = [C.c_char_p]
     lib.mvp_sizeof.restype = _i
     lib.mvp_bn_tokens_workspace_bytes.argtypes = [_i, _i]

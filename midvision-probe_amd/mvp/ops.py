@@ -490,3 +490,10 @@ def corr_argmax(src_feat, tgt_feat, kp_xy, out_xy, out_val, workspace, Cdim, h, 
     a = lib.CorrArgmaxArgs(lib.ptr(src_feat), lib.ptr(tgt_feat), lib.ptr(kp_xy), lib.ptr(out_xy), lib.ptr(out_val), lib.ptr(workspace),
                            workspace.numel() * workspace.element_size(), Cdim, h, w, K, lib.ptr(heat_out))
     lib.call("mvp_corr_argmax", a)
+
+
+def knn_ratio(src_feat, tgt_feat, src_valid, tgt_valid, nn_idx, dist, weight, n_valid, workspace, Cdim, N0, N1) -> None:
+    """Top-2 cosine nearest neighbours of every valid query among the valid targets + the ratio-test weight (include/mvp_hip.h)."""
+    a = lib.KnnRatioArgs(lib.ptr(src_feat), lib.ptr(tgt_feat), lib.ptr(src_valid), lib.ptr(tgt_valid), lib.ptr(nn_idx), lib.ptr(dist),
+                         lib.ptr(weight), lib.ptr(n_valid), lib.ptr(workspace), workspace.numel() * workspace.element_size(), Cdim, N0, N1)
+    lib.call("mvp_knn_ratio", a)
