@@ -82,6 +82,9 @@ typedef struct {
                                 bias); three new exports, each with its own tagged argument struct, no existing struct changed.
                                 Added within 8: mvp_knn_ratio and mvp_knn_workspace_bytes (top-2 cosine nearest neighbours with the ratio test,
                                 NAVI / ScanNet 3-D correspondence); a new export with its own tagged argument struct, no existing struct changed.
+                                Added within 8: mvp_bn_act_fwd, mvp_bn_act_bwd, mvp_bce_loss_fwd_bwd and mvp_binary_counts (the tail of the objectness
+                                probe: BatchNorm2d + sigmoid on a few-channel map, BCELoss, confusion counts); new exports with their own tagged
+                                argument structs, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -672,6 +675,76 @@ struct mvp_knn_ratio_args {
  * T = ceil(N1 / 128) target tiles.  0 for sizes that mvp_knn_ratio rejects. */
 int64_t mvp_knn_workspace_bytes(int C, int N0, int N1);
 int mvp_knn_ratio(const mvp_knn_ratio_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; new exports with their own tagged argument structs, no existing struct changed.)
+ * The tail of the objectness probe (evals/models/probes.py:7-43 BinaryHead / TaskonomyHead, train_generic_objectness.py).
+ *
+ * mvp_bn_act_fwd / mvp_bn_act_bwd: nn.BatchNorm2d(C) followed by an activation, on the head's channels-last logits.
+ *   x [P, ld] fp32, P = B * HW rows, channel c in column c, 1 <= C <= MVP_BN_ACT_MAX_C, ld >= C; columns C..ld-1 never enter a result.
+ *   y [B, C, HW] fp32 (the NCHW tensor the caller resizes).
+ *   act MVP_BN_ACT_SIGMOID: z = (x - mean) * rstd * gamma + beta, y = sigmoid(z), rstd = 1 / sqrt(var + eps).
+ *       training != 0: mean and BIASED variance of the P rows; running_mean / running_var (both or neither; NULL = not tracked)
+ *       move by `momentum`, running_var towards var * n / (n - 1) with the count n of the arguments (a caller that normalises
+ *       before a nearest x2 upsample passes n = 4 P: the statistics of the upsampled map), num_batches_tracked[0] += 1 (NULL: skipped).
+ *       training == 0: the running statistics, nothing updated.
+ *       The variance is merged from (count, mean, M2) partials (Chan et al.), never E[x^2] - E[x]^2.
+ *       stats [3 C] is written by the forward and read by the backward: mean, rstd, then the part of the mean that fp32 dropped.
+ *   act MVP_BN_ACT_TANH: y = tanh(x);  MVP_BN_ACT_NONE: y = x.  Neither normalises; gamma / beta / stats / workspace are unused.
+ *   bwd: grad_y [B, C, HW] -> grad_x [P, ld] (columns C..ld-1 written as zero; NULL: parameter gradients only), with g_z =
+ *       grad_y * act'(z) recomputed from x: training  grad_x = gamma rstd (g_z - dbeta / P - xhat dgamma / P),  eval  gamma rstd g_z;
+ *       grad_beta [C] = sum g_z, grad_gamma [C] = sum g_z xhat (either may be NULL; accumulate != 0: added to what is there).
+ *   Reductions: per-workgroup fp64 partials in the workspace, folded in a fixed order; two calls give the same bits.
+ *   MVP_EINVAL: NULL x / y (fwd) / grad_y (bwd), B, HW <= 0, C outside 1..8, ld < C, an unknown act; for the sigmoid form NULL gamma /
+ *   beta / stats / workspace or workspace_bytes < MVP_BN_ACT_WORKSPACE_BYTES, training with P < 2 or n < 2 (torch refuses one value
+ *   per channel), eval without running statistics; bwd with nothing to write.
+ * ---------------------------------------------------------------------------------- */
+#define MVP_BN_ACT_MAX_C 8
+#define MVP_BN_ACT_NONE 0
+#define MVP_BN_ACT_SIGMOID 1
+#define MVP_BN_ACT_TANH 2
+#define MVP_BN_ACT_WORKSPACE_BYTES 98304 /* 512 partial rows x 8 channels x 3 fp64 */
+typedef struct mvp_bn_act_args mvp_bn_act_args;
+struct mvp_bn_act_args {
+  const float* x; float* y;
+  const float* gamma; const float* beta;
+  float* running_mean; float* running_var; int64_t* num_batches_tracked;
+  float* stats;
+  const float* grad_y; float* grad_x; float* grad_gamma; float* grad_beta;
+  void* workspace; int64_t workspace_bytes;
+  int B; int64_t HW; int C; int ld;
+  int64_t n;
+  float eps, momentum;
+  int act, training, accumulate;
+};
+int mvp_bn_act_fwd(const mvp_bn_act_args*, void* stream);
+int mvp_bn_act_bwd(const mvp_bn_act_args*, void* stream);
+
+/* nn.BCELoss() (mean reduction) and its gradient in one launch chain (train_generic_objectness.py:395,575).
+ * pred, target [N] fp32 in [0, 1].  loss[0] = mean of -(t max(log p, -100) + (1 - t) max(log1p(-p), -100)) (torch's clamp);
+ * grad_pred [N] (NULL: loss only) = (p - t) / max((1 - p) p, 1e-12) / N.  At p in {0, 1}: 100 and -+1e12 / N against the other
+ * target, 0 and 0 against its own.  fp64 partial sums in the workspace, folded in a fixed order.
+ * MVP_EINVAL: NULL pred / target / loss / workspace, N <= 0, workspace_bytes < MVP_BCE_WORKSPACE_BYTES or not 8-byte aligned. */
+#define MVP_BCE_WORKSPACE_BYTES 8192
+typedef struct mvp_bce_loss_args mvp_bce_loss_args;
+struct mvp_bce_loss_args {
+  const float* pred; const float* target; float* loss; float* grad_pred;
+  void* workspace; int64_t workspace_bytes;
+  int64_t N;
+};
+int mvp_bce_loss_fwd_bwd(const mvp_bce_loss_args*, void* stream);
+
+/* Confusion counts of a thresholded prediction (train_generic_objectness.py:56-183 count these with numpy on the host).
+ * pred, gt [G, n] fp32, gt holding exactly 0 or 1; counts [G, 4] int64 = TP, FP, FN, TN with "positive" = pred > threshold
+ * (strictly; NaN is negative).  G = 1, n = B H W is the reference's whole-batch form; G = B gives per-image counts.  The op zeroes
+ * counts itself.  MVP_EINVAL: a NULL pointer, G <= 0 or G > 65535, n <= 0, counts not 8-byte aligned. */
+typedef struct mvp_binary_counts_args mvp_binary_counts_args;
+struct mvp_binary_counts_args {
+  const float* pred; const float* gt; int64_t* counts;
+  int G; int64_t n;
+  float threshold;
+};
+int mvp_binary_counts(const mvp_binary_counts_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution weight re-layout (per step; the probe's conv weights are trained):

@@ -33,3 +33,49 @@ class SyntheticNYU(Dataset):
         blobs = torch.randint(0, 150, ((H + 15) // 16, (W + 15) // 16), generator=g)
         out["segmentation"] = blobs.repeat_interleave(16, 0).repeat_interleave(16, 1)[:H, :W].contiguous()
         return out
+
+
+class SyntheticVOC(Dataset):
+    """VOC-shaped synthetic objectness samples honouring the reference's per-sample dict contract (evals/datasets/voc.py):
+    {"original_image": float32 [3,S,S] ImageNet-normalised, "original_image_rgb": float32 [3,S,S] in [0,1], "gt_binary_mask": float32
+    [1,S,S] of exact 0 / 1, "num_objects": int}.  The mask is the union of one to three seeded rectangles or ellipses (never empty,
+    never the whole image) and the image is brighter inside it, so a probe has something to learn.  Samples are a pure function of
+    (seed, split, index); splits: "trainval" and "test"."""
+
+    MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+    def __init__(self, split: str = "trainval", num_samples: int = 64, fixed_size: int = 480, seed: int = 0, name: str = "voc"):
+        if split not in ("trainval", "test"):
+            raise ValueError(f"SyntheticVOC: split {split!r} (expected 'trainval' or 'test')")
+        self.split, self.n, self.size, self.seed, self.name = split, int(num_samples), int(fixed_size), int(seed), name
+        self._salt = {"trainval": 0, "test": 1}[split]
+
+    def __len__(self) -> int:
+        return self.n
+
+    def __getitem__(self, i: int):
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        g = torch.Generator().manual_seed((self.seed * 2 + self._salt) * 1_000_003 + i + 77_000_000)
+        S = self.size
+        num_objects = int(torch.randint(1, 4, (1,), generator=g))
+        ys = torch.arange(S, dtype=torch.float32).view(S, 1)
+        xs = torch.arange(S, dtype=torch.float32).view(1, S)
+        mask = torch.zeros(S, S, dtype=torch.bool)
+        for _ in range(num_objects):
+            u = torch.rand(5, generator=g)
+            # half-extents between an eighth and a quarter of the side, centre kept inside the image: the union of three shapes covers at most
+            # 3/4 of it, a single one at least one pixel
+            ry, rx = float(S * (0.125 + 0.125 * u[0])), float(S * (0.125 + 0.125 * u[1]))
+            cy, cx = float(u[2] * (S - 1)), float(u[3] * (S - 1))
+            if u[4] < 0.5:
+                shape = ((ys - cy).abs() <= ry) & ((xs - cx).abs() <= rx)
+            else:
+                shape = ((ys - cy) / ry) ** 2 + ((xs - cx) / rx) ** 2 <= 1.0
+            mask |= shape
+        rgb = torch.rand(3, S, S, generator=g) * 0.5
+        rgb = torch.where(mask, rgb + 0.5, rgb).clamp_(0.0, 1.0)
+        mean = torch.tensor(self.MEAN).view(3, 1, 1)
+        std = torch.tensor(self.STD).view(3, 1, 1)
+        return {"original_image": (rgb - mean) / std, "original_image_rgb": rgb, "gt_binary_mask": mask.float().unsqueeze(0),
+                "num_objects": num_objects}

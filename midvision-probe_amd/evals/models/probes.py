@@ -1,4 +1,4 @@
-"""evals.models.probes — drop-in for the reference's probe heads (evals/models/probes.py:86-459):
+"""evals.models.probes — drop-in for the reference's probe heads (evals/models/probes.py:7-459):
 same class names, constructor kwargs, ``.name`` strings and state-dict keys
 (``head.conv.weight``, ``head.conv_0.weight``, ``head.ref_0.resConfUnit1.conv.0.weight`` ...),
 forward/backward on the HIP kernels (mvp.functional).
@@ -23,6 +23,60 @@ def _precision(p):
     from mvp import lib
 
     return lib.PREC_BF16X3 if pr == lib.PREC_F16X2 else pr
+
+
+class _SigmoidMapHead(nn.Module):
+    """The shared body of BinaryHead and TaskonomyHead (reference: probes.py:7-43 and :46-83, the same class body twice) — a Linear /
+    Multiscale / DPT trunk, then (``pred_type`` "sigmoid") BatchNorm2d + sigmoid, ("tanh") tanh, (anything else) the raw logits.
+    ``batch_norm`` is the reference's nn.BatchNorm2d as the container of the affine parameters and the running statistics (state-dict
+    keys ``batch_norm.*``); its arithmetic runs in mvp.functional.bn_act, with ``self.training`` choosing batch or running statistics."""
+
+    def __init__(self, feat_dim, head_type, uncertainty_aware, hidden_dim, kernel_size, output_dim, pred_type, precision):
+        super().__init__()
+        self.uncertainty_aware = uncertainty_aware
+        self.kernel_size = kernel_size
+        assert head_type in ["linear", "multiscale", "dpt"]
+        name = f"snorm_{head_type}_k{kernel_size}"  # (the reference's string: checkpoint paths are built from it)
+        self.name = f"{name}_UA" if uncertainty_aware else name
+        self.pred_type = pred_type
+        if pred_type == "sigmoid":
+            self.batch_norm = nn.BatchNorm2d(output_dim)
+        if head_type == "linear":
+            self.head = Linear(feat_dim, output_dim, kernel_size, precision=precision)
+        elif head_type == "multiscale":
+            self.head = MultiscaleHead(feat_dim, output_dim, hidden_dim, kernel_size, precision=precision)
+        else:
+            self.head = DPT(feat_dim, output_dim, hidden_dim, kernel_size, precision=precision)
+
+    def forward(self, feats):
+        act = self.pred_type if self.pred_type in ("sigmoid", "tanh") else "none"
+        bn = self.batch_norm if act == "sigmoid" else None
+        if isinstance(self.head, DPT):
+            # DPT ends in a nearest x2: every logit appears four times, so the batch mean and the biased variance of the upsampled map
+            # are those of the map before it, and a per-pixel activation commutes with the replication.  Normalise at 8h x 8w, then
+            # upsample; only the unbiased running variance sees the count, which is 4 x the pixels normalised here (n_factor).
+            y = MF.bn_act(self.head(feats, defer_upsample=True), bn, act, self.training, n_factor=4)
+            return MF.interpolate(y, scale_factor=2, mode="nearest")
+        x = self.head(feats)
+        if act == "none":
+            return x
+        return MF.bn_act(x, bn, act, self.training)
+
+
+class BinaryHead(_SigmoidMapHead):
+    """Reference: probes.py:7-43."""
+
+    def __init__(self, feat_dim, head_type="dpt", uncertainty_aware=False, hidden_dim=512, kernel_size=1, output_dim=2, pred_type="sigmoid",
+                 precision=None):
+        super().__init__(feat_dim, head_type, uncertainty_aware, hidden_dim, kernel_size, output_dim, pred_type, precision)
+
+
+class TaskonomyHead(_SigmoidMapHead):
+    """Reference: probes.py:46-83 — BinaryHead with ``output_dim`` defaulting to 1."""
+
+    def __init__(self, feat_dim, head_type="dpt", uncertainty_aware=False, hidden_dim=512, kernel_size=1, output_dim=1, pred_type="sigmoid",
+                 precision=None):
+        super().__init__(feat_dim, head_type, uncertainty_aware, hidden_dim, kernel_size, output_dim, pred_type, precision)
 
 
 class SurfaceNormalHead(nn.Module):

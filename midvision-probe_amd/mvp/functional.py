@@ -6,6 +6,7 @@ the HIP kernels through the C ABI; PyTorch only provides the tape, memory and st
                      conv1x1 at token resolution then bilinear x4 (the two commute; 16x less work)
   depth_bins / depth_sigmoid   probes.py:176-212
   depth_loss / angular_loss    evals/utils/losses.py:97-182
+  bn_act / bce_loss            probes.py:36-43 (BinaryHead's BatchNorm2d + sigmoid), train_generic_objectness.py:395 (nn.BCELoss)
 """
 from __future__ import annotations
 
@@ -258,23 +259,31 @@ class _LinearHeadKxK(torch.autograd.Function):
         B, _, h, w = feats[0].shape
         dev = weight.device
         K, Ctot, k, _ = weight.shape
-        if Ctot % 128:
-            raise lib.MvpError("Linear(k>1) on the HIP path needs sum(feat_dim) % 128 == 0")
+        # the implicit-GEMM conv and the TN weight-gradient kernel take input channels in multiples of 128: other widths run with
+        # zero channels appended to the packed map and to the weight (they add nothing to the output; their gradient is dropped)
+        Cp = (Ctot + 127) // 128 * 128
         H4, W4 = 4 * h, 4 * w
         M = B * H4 * W4
-        up = ops.empty_pair((M, Ctot), precision, dev)
+        up = ops.empty_pair((M, Cp), precision, dev)
+        wsrc = weight.detach()
+        if Cp != Ctot:
+            for t in up:
+                if t is not None:
+                    t.zero_()
+            wsrc = wsrc.new_zeros(K, Cp, k, k)
+            wsrc[:, :Ctot] = weight.detach()
         off = 0
         for f in feats:  # bilinear x4 per map (planar kernel), packed channels-last at its channel offset
             C = int(f.shape[1])
             big = torch.empty(B, C, H4, W4, dtype=torch.float32, device=dev)
             ops.resize(f.contiguous().float(), big, B * C, h, w, H4, W4, lib.RESIZE_BILINEAR, scale_h=4.0, scale_w=4.0)
-            ops.pack_nchw_tokens(big, B, C, H4 * W4, tok=up, ld_tok=Ctot, col_off=off)
+            ops.pack_nchw_tokens(big, B, C, H4 * W4, tok=up, ld_tok=Cp, col_off=off)
             off += C
         K4 = (K + 3) // 4 * 4
-        g = cv.geom(B, H4, W4, Ctot, k, k, 1, k // 2)
+        g = cv.geom(B, H4, W4, Cp, k, k, 1, k // 2)
         b4 = torch.cat([bias.detach().float(), bias.new_zeros(K4 - K).float()]) if K4 != K else bias.detach().float().contiguous()
         lq = torch.empty(B, H4, W4, K4, dtype=torch.float32, device=dev)
-        cv.conv_gemm(up, g, cv.pack_weight(weight, 0, precision, pad_cout_to=K4), K4, bias=b4, out_f32=lq, precision=precision)
+        cv.conv_gemm(up, g, cv.pack_weight(wsrc, 0, precision, pad_cout_to=K4), K4, bias=b4, out_f32=lq, precision=precision)
         ctx.up, ctx.g, ctx.cfg = up, g, (K, K4, M, precision)
         ctx.wshape = weight.shape
         return lq
@@ -288,8 +297,11 @@ class _LinearHeadKxK(torch.autograd.Function):
         gl = glq.contiguous().float().reshape(M, K4)
         LG = (K4 + 127) // 128 * 128
         gP = cv.mask_split(gl, None, M, K4, ldo=LG, precision=pr)
-        dW = torch.empty(ctx.wshape, dtype=torch.float32, device=dev)
-        cv.conv_dw(gP, LG, ctx.up, ctx.g["C"], ctx.g, K, dW, precision=pr)
+        Cp, Ctot = ctx.g["C"], ctx.wshape[1]
+        dW = torch.empty((ctx.wshape[0], Cp) + tuple(ctx.wshape[2:]), dtype=torch.float32, device=dev)
+        cv.conv_dw(gP, LG, ctx.up, Cp, ctx.g, K, dW, precision=pr)
+        if Cp != Ctot:
+            dW = dW[:, :Ctot].contiguous()
         db = torch.empty(K4, dtype=torch.float32, device=dev)
         ops.colsum(gl, db, M, K4)
         return dW, db[:K].contiguous(), None, None
@@ -481,3 +493,100 @@ def angular_loss(pred, gt, mask, uncertainty_aware=False, eps=1e-4):
     assert mask.ndim == 4, f"mask should be (batch x height x width) not {mask.shape}"
     assert pred.shape[1] == (4 if uncertainty_aware else 3)
     return _AngularLoss.apply(pred, gt, mask, float(eps))
+
+
+# --------------------------------------------------------------------------- objectness tail: BatchNorm2d + activation, BCELoss
+_BN_ACTS = {"none": lib.BN_ACT_NONE, "sigmoid": lib.BN_ACT_SIGMOID, "tanh": lib.BN_ACT_TANH}
+
+
+def _rows_view(x: torch.Tensor):
+    """NCHW logits (usually the permuted view of a head's channels-last buffer [B, H, W, ld]) -> (tensor whose memory is the
+    [B*H*W, ld] row-major map, ld).  No copy when x already is such a view."""
+    B, Cdim, H, W = x.shape
+    sb, sc, sh, sw = x.stride()
+    ld = sw
+    if x.dtype == torch.float32 and (sc == 1 or Cdim == 1) and ld >= Cdim and sh == W * ld and sb == H * W * ld:
+        return x, ld
+    return x.permute(0, 2, 3, 1).contiguous().float(), Cdim  # [B, H, W, C]: same first element, rows of C
+
+
+class _BnAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bn, act, training, n_factor):
+        _need_cuda(x, "bn_act")
+        B, Cdim, H, W = x.shape
+        HW = H * W
+        xr, ld = _rows_view(x)
+        dev = x.device
+        y = torch.empty(B, Cdim, H, W, dtype=torch.float32, device=dev)
+        stats = ws = None
+        kw = {}
+        if act == lib.BN_ACT_SIGMOID:
+            stats = torch.empty(3 * Cdim, dtype=torch.float32, device=dev)
+            ws = ops.bn_act_workspace(dev)
+            kw = dict(gamma=gamma.detach(), beta=beta.detach(), stats=stats, workspace=ws, n=n_factor * B * HW, eps=float(bn.eps),
+                      momentum=float(bn.momentum), running_mean=bn.running_mean, running_var=bn.running_var,
+                      num_batches_tracked=bn.num_batches_tracked if training else None)
+        ops.bn_act_fwd(xr, y, B, HW, Cdim, ld, act, training, **kw)
+        ctx.save_for_backward(xr, stats if stats is not None else y)
+        ctx.cfg = (B, Cdim, H, W, ld, act, training, tuple(x.shape), tuple(x.stride()))
+        ctx.params = (gamma, beta)
+        ctx.ws = ws
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xr, stats = ctx.saved_tensors
+        B, Cdim, H, W, ld, act, training, shape, stride = ctx.cfg
+        gamma, beta = ctx.params
+        dev = gy.device
+        gy = gy.contiguous().float()
+        gx = torch.empty(B, H, W, ld, dtype=torch.float32, device=dev)
+        dg = db = None
+        kw = {}
+        if act == lib.BN_ACT_SIGMOID:
+            dg, db = _grad_dst(gamma, (Cdim,)), _grad_dst(beta, (Cdim,))
+            dg = dg if dg is not None else torch.empty(Cdim, dtype=torch.float32, device=dev)
+            db = db if db is not None else torch.empty(Cdim, dtype=torch.float32, device=dev)
+            kw = dict(gamma=gamma.detach(), beta=beta.detach(), stats=stats, workspace=ctx.ws, grad_gamma=dg, grad_beta=db)
+        ops.bn_act_bwd(xr, gy, gx, B, H * W, Cdim, ld, act, training, **kw)
+        return gx[..., :Cdim].permute(0, 3, 1, 2), dg, db, None, None, None, None
+
+
+def bn_act(x: torch.Tensor, bn=None, act: str = "sigmoid", training: bool = True, n_factor: int = 1) -> torch.Tensor:
+    """``act(bn(x))`` for NCHW logits of at most 8 channels (probes.py:36-43): ``bn`` is the nn.BatchNorm2d that holds the affine
+    parameters and the running statistics (train mode: batch statistics, running statistics and num_batches_tracked updated in
+    place; eval mode: running statistics).  ``act`` "tanh" / "none" apply no normalisation (``bn`` unused).  ``n_factor``: the count
+    behind the unbiased running variance is n_factor x the pixels of x (4 when a nearest x2 upsample follows: BinaryHead over DPT)."""
+    a = _BN_ACTS[act]
+    if a == lib.BN_ACT_SIGMOID:
+        if bn is None or not bn.affine or not bn.track_running_stats or bn.momentum is None:
+            raise lib.MvpError("bn_act: the sigmoid form needs an affine nn.BatchNorm2d with running statistics and a fixed momentum")
+        return _BnAct.apply(x, bn.weight, bn.bias, bn, a, bool(training), int(n_factor))
+    return _BnAct.apply(x, None, None, None, a, False, 1)
+
+
+class _BceLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        _need_cuda(pred, "bce_loss")
+        if tuple(pred.shape) != tuple(target.shape):
+            raise ValueError(f"bce_loss: prediction {tuple(pred.shape)} and target {tuple(target.shape)} differ (nn.BCELoss does not broadcast)")
+        p = pred.contiguous().float()
+        t = target.contiguous().float()
+        out = torch.empty(1, dtype=torch.float32, device=p.device)
+        grad = torch.empty_like(p)
+        ws = torch.empty(lib.BCE_WORKSPACE_BYTES // 8, dtype=torch.float64, device=p.device)
+        ops.bce_loss(p, t, out, grad, ws, p.numel())
+        ctx.save_for_backward(grad)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return _scaled(grad, g), None
+
+
+def bce_loss(pred, target):
+    """``nn.BCELoss()(pred, target)`` (mean; log terms clamped at -100) with its gradient from the same launch chain."""
+    return _BceLoss.apply(pred, target)

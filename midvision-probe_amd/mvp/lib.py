@@ -22,6 +22,8 @@ PREC_F16X2 = 2  # two fp16 products per GEMM contraction over compensated fp16 p
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_QUICK_GELU, ACT_GELU_TANH = 0, 1, 2, 3, 4  # MVP_ACT_*
 RESIZE_NEAREST, RESIZE_BILINEAR, RESIZE_BICUBIC = 0, 1, 2
 PAIR_SEPARATE, PAIR_A_ILV32, PAIR_W_ILV32 = 0, 1, 2  # mvp_gemm_args.pair_layout (bit flags)
+BN_ACT_NONE, BN_ACT_SIGMOID, BN_ACT_TANH = 0, 1, 2  # MVP_BN_ACT_*
+BN_ACT_WORKSPACE_BYTES, BCE_WORKSPACE_BYTES = 98304, 8192  # MVP_BN_ACT_WORKSPACE_BYTES, MVP_BCE_WORKSPACE_BYTES
 BN_RUNNING_MAX = 8  # MVP_BN_RUNNING_MAX: modules per mvp_bn_running_update_n launch
 TILES_SHARED, TILES_NO_PP, TILES_NO_UNI = 1, 2, 4
 ROUTE_PP, ROUTE_TILE, ROUTE_SPLITK, ROUTE_CONV = 1, 2, 3, 4  # mvp_gemm_route_t.family
@@ -178,6 +180,20 @@ class KnnRatioArgs(C.Structure):  # mvp_knn_ratio_args: top-2 cosine nearest nei
                 ("n_valid", _vp), ("workspace", _vp), ("workspace_bytes", _i64), ("C", _i), ("N0", _i), ("N1", _i)]
 
 
+class BnActArgs(C.Structure):  # mvp_bn_act_args: BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
+    _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
+                ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+                ("B", _i), ("HW", _i64), ("C", _i), ("ld", _i), ("n", _i64), ("eps", _f), ("momentum", _f), ("act", _i), ("training", _i), ("accumulate", _i)]
+
+
+class BceLossArgs(C.Structure):  # mvp_bce_loss_args: nn.BCELoss (mean) and its gradient (added within ABI 8)
+    _fields_ = [("pred", _vp), ("target", _vp), ("loss", _vp), ("grad_pred", _vp), ("workspace", _vp), ("workspace_bytes", _i64), ("N", _i64)]
+
+
+class BinaryCountsArgs(C.Structure):  # mvp_binary_counts_args: TP / FP / FN / TN of a thresholded prediction (added within ABI 8)
+    _fields_ = [("pred", _vp), ("gt", _vp), ("counts", _vp), ("G", _i), ("n", _i64), ("threshold", _f)]
+
+
 class ScaleShiftArgs(C.Structure):
     _fields_ = [("x", _vp), ("scale_shift", _vp), ("grad_out", _vp), ("out", _vp), ("B", _i), ("HW", _i64), ("lo", _f), ("hi", _f),
                 ("clamp", _i), ("backward", _i)]
@@ -309,6 +325,10 @@ SYMBOLS = {
     "mvp_attention_relpos_fwd": AttentionRelposArgs,
     "mvp_knn_ratio": KnnRatioArgs,
     "mvp_knn_workspace_bytes": None,
+    "mvp_bn_act_fwd": BnActArgs,
+    "mvp_bn_act_bwd": BnActArgs,
+    "mvp_bce_loss_fwd_bwd": BceLossArgs,
+    "mvp_binary_counts": BinaryCountsArgs,
 }
 
 # the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
@@ -316,7 +336,9 @@ NEW_STRUCTS_ABI7 = {"mvp_gemm_scaled_args": GemmScaledArgs, "mvp_patch_gather_ld
 
 NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs, "mvp_attention_bias_args": AttentionBiasArgs,
                     "mvp_gather_rows_args": GatherRowsArgs, "mvp_relpos_terms_args": RelposTermsArgs,
-                    "mvp_attention_relpos_args": AttentionRelposArgs, "mvp_knn_ratio_args": KnnRatioArgs}  # the same for the additions of / within ABI 8
+                    "mvp_attention_relpos_args": AttentionRelposArgs, "mvp_knn_ratio_args": KnnRatioArgs,
+                    "mvp_bn_act_args": BnActArgs, "mvp_bce_loss_args": BceLossArgs,
+                    "mvp_binary_counts_args": BinaryCountsArgs}  # the same for the additions of / within ABI 8
 
 _lib: Optional[C.CDLL] = None
 

@@ -497,3 +497,45 @@ def knn_ratio(src_feat, tgt_feat, src_valid, tgt_valid, nn_idx, dist, weight, n_
     a = lib.KnnRatioArgs(lib.ptr(src_feat), lib.ptr(tgt_feat), lib.ptr(src_valid), lib.ptr(tgt_valid), lib.ptr(nn_idx), lib.ptr(dist),
                          lib.ptr(weight), lib.ptr(n_valid), lib.ptr(workspace), workspace.numel() * workspace.element_size(), Cdim, N0, N1)
     lib.call("mvp_knn_ratio", a)
+
+
+def bn_act_workspace(device) -> torch.Tensor:
+    """A workspace for bn_act_fwd / bn_act_bwd (MVP_BN_ACT_WORKSPACE_BYTES of fp64 partials)."""
+    return torch.empty(lib.BN_ACT_WORKSPACE_BYTES // 8, dtype=torch.float64, device=device)
+
+
+def _bn_act_args(x, B, HW, Cdim, ld, act, training, *, y=None, gamma=None, beta=None, running_mean=None, running_var=None,
+                 num_batches_tracked=None, stats=None, grad_y=None, grad_x=None, grad_gamma=None, grad_beta=None, workspace=None, n=0,
+                 eps=1e-5, momentum=0.1, accumulate=False):
+    return lib.BnActArgs(lib.ptr(x), lib.ptr(y), lib.ptr(gamma), lib.ptr(beta), lib.ptr(running_mean), lib.ptr(running_var),
+                         lib.ptr(num_batches_tracked), lib.ptr(stats), lib.ptr(grad_y), lib.ptr(grad_x), lib.ptr(grad_gamma), lib.ptr(grad_beta),
+                         lib.ptr(workspace), workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                         B, HW, Cdim, ld, int(n), eps, momentum, act, int(training), int(accumulate))
+
+
+def bn_act_fwd(x, y, B, HW, Cdim, ld, act, training, **kw) -> None:
+    """BatchNorm2d + activation of channels-last logits x [B*HW, ld] -> y [B, C, HW] (include/mvp_hip.h: mvp_bn_act_fwd)."""
+    a = _bn_act_args(x, B, HW, Cdim, ld, act, training, y=y, **kw)
+    # algorithmic HBM bytes: the C used columns read (twice when the batch statistics are taken first), y written
+    work = float(B * HW * Cdim * 4 * (3 if (act == lib.BN_ACT_SIGMOID and training) else 2))
+    _traced("hbm", "bn_act_fwd", 0, work, lambda: lib.call("mvp_bn_act_fwd", a))
+
+
+def bn_act_bwd(x, grad_y, grad_x, B, HW, Cdim, ld, act, training, **kw) -> None:
+    """grad_y [B, C, HW] -> grad_x [B*HW, ld] (+ grad_gamma / grad_beta of the sigmoid form): mvp_bn_act_bwd."""
+    a = _bn_act_args(x, B, HW, Cdim, ld, act, training, grad_y=grad_y, grad_x=grad_x, **kw)
+    work = float(B * HW * 4 * ((4 if act == lib.BN_ACT_SIGMOID else 2) * Cdim + ld))
+    _traced("hbm", "bn_act_bwd", 0, work, lambda: lib.call("mvp_bn_act_bwd", a))
+
+
+def bce_loss(pred, target, loss, grad_pred, workspace, N) -> None:
+    """nn.BCELoss (mean) of pred / target [N] and its gradient (grad_pred may be None): mvp_bce_loss_fwd_bwd."""
+    a = lib.BceLossArgs(lib.ptr(pred), lib.ptr(target), lib.ptr(loss), lib.ptr(grad_pred), lib.ptr(workspace),
+                        workspace.numel() * workspace.element_size(), N)
+    _traced("hbm", "bce_loss", 0, float(N * (12 if grad_pred is not None else 8)), lambda: lib.call("mvp_bce_loss_fwd_bwd", a))
+
+
+def binary_counts(pred, gt, counts, G, n, threshold=0.5) -> None:
+    """counts [G, 4] int64 = TP, FP, FN, TN of (pred > threshold) against gt in {0, 1}, pred / gt [G, n]: mvp_binary_counts."""
+    a = lib.BinaryCountsArgs(lib.ptr(pred), lib.ptr(gt), lib.ptr(counts), G, n, threshold)
+    _traced("hbm", "binary_counts", 0, float(G * n * 8), lambda: lib.call("mvp_binary_counts", a))

@@ -1,6 +1,6 @@
-"""The hot loop bodies of train_depth.py:93-144 and train_snorm.py:86-120, on the HIP path.
+"""The hot loop bodies of train_depth.py:93-144, train_snorm.py:86-120 and train_generic_objectness.py:372-398, on the HIP path.
 
-``train_depth_step`` / ``train_snorm_step`` are the per-batch bodies (what bench.py times);
+``train_depth_step`` / ``train_snorm_step`` / ``train_objectness_step`` are the per-batch bodies (bench.py times the first);
 ``train`` mirrors the reference's ``train()`` signature for drop-in use.
 """
 from __future__ import annotations
@@ -79,6 +79,23 @@ def train_snorm_step(model, probe, optimizer, scheduler, images, target, mask, d
     pred = MF.interpolate(pred.contiguous(), size=target.shape[-2:], mode="bicubic")
     uncertainty = pred.shape[1] > 3
     loss = angular_loss(pred, target, mask, uncertainty_aware=uncertainty)
+    MF.backward(loss)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach()
+
+
+def train_objectness_step(model, probe, optimizer, scheduler, images, target, detach_model=True, feats=None):
+    """One iteration of train_generic_objectness.py:372-398 (bilinear resize to the mask, nn.BCELoss); returns the loss as a device
+    scalar.  ``target``: the float 0 / 1 mask [B, C, H, W] with the probe's channel count.  ``feats`` as in ``train_depth_step``."""
+    optimizer.zero_grad()
+    if feats is None:
+        feats = extract_features(model, images, detach_model)
+    _finish_pending(optimizer)
+    pred = probe(feats)
+    pred = MF.interpolate(pred, size=target.shape[-2:], mode="bilinear")
+    loss = MF.bce_loss(pred, target)
     MF.backward(loss)
     optimizer.step()
     if scheduler is not None:
