@@ -85,6 +85,8 @@ typedef struct {
                                 Added within 8: mvp_bn_act_fwd, mvp_bn_act_bwd, mvp_bce_loss_fwd_bwd and mvp_binary_counts (the tail of the objectness
                                 probe: BatchNorm2d + sigmoid on a few-channel map, BCELoss, confusion counts); new exports with their own tagged
                                 argument structs, no existing struct changed.
+                                Added within 8: mvp_pointcloud_sample (zero-padded bilinear sampling of a feature map at the projections of a point
+                                cloud, ScanNet pair correspondence); a new export with its own tagged argument struct, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -675,6 +677,37 @@ struct mvp_knn_ratio_args {
  * T = ceil(N1 / 128) target tiles.  0 for sizes that mvp_knn_ratio rejects. */
 int64_t mvp_knn_workspace_bytes(int C, int N0, int N1);
 int mvp_knn_ratio(const mvp_knn_ratio_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed.)
+ * Dense features sampled at the projections of a point cloud: the depth path in front of mvp_knn_ratio in the ScanNet pair
+ * correspondence evaluation (evals/utils/correspondence.py:164-176, sample_pointcloud_features = projection by K, then
+ * grid_sample(mode="bilinear", padding_mode="zeros", align_corners=False)).  Definition, per point p = pc[n]:
+ *     uvd = K p,   u = uvd.x / max(uvd.z, 1e-9),   v = uvd.y / max(uvd.z, 1e-9)
+ *     x = u * fw / W - 0.5,   y = v * fh / H - 0.5          (= ((2 u / W - 1) + 1) * fw / 2 - 0.5)
+ *     out[c, n] = sum over the 4 corners (floor / floor + 1 of x and y) of w_corner * feat[c, yc, xc]
+ * A corner outside [0, fw - 1] x [0, fh - 1] contributes 0 (its texel is not used, whatever it holds).  A point whose x or y is not
+ * finite or lies outside (-1, fw) x (-1, fh) gives exactly 0.0f in every channel; that is decided on the floats, before any
+ * conversion to int (z = 0 and z < 0 reach u ~ 1e9 x through the clamp; a NaN coordinate reaches both u and v).  The point 0 itself, which
+ * a depth hole back-projects to, has u = v = 0 and so samples the corner texel at a quarter weight, as grid_sample does: mask by valid.
+ * out is channel-major with column n = point n, the layout mvp_knn_ratio reads; columns N..ld_out-1 are never written.
+ * valid[n] (optional) = pc[n].z > 0, the reference's test for a real point.
+ * One launch: lanes along the points, corner offsets and weights once per point, the grid cut over chunks of 16 channels.
+ * No atomics, no sync, no allocation, no workspace; two calls give the same bits.
+ * MVP_EINVAL: a NULL pointer other than valid, a size <= 0, ld_out < N, N > 2^24.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_pointcloud_sample_args mvp_pointcloud_sample_args;
+struct mvp_pointcloud_sample_args {
+  const float* feat;  /* [C, fh, fw] fp32                                                    */
+  const float* pc;    /* [N, 3] fp32 camera-frame points                                     */
+  const float* K;     /* [3, 3] fp32 intrinsics ON THE DEVICE (row-major)                    */
+  float* out;         /* [C, ld_out] fp32                                                    */
+  uint8_t* valid;     /* optional [N]: 1 where pc[n].z > 0; NULL = not wanted                */
+  int C, fh, fw, N;
+  int H, W;           /* the image (depth grid) size K projects into                         */
+  int ld_out;         /* >= N                                                                */
+};
+int mvp_pointcloud_sample(const mvp_pointcloud_sample_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * (added within ABI 8; new exports with their own tagged argument structs, no existing struct changed.)

@@ -3,8 +3,11 @@
 
 ``knn_ratio`` runs the fused HIP path (mvp_knn_ratio: L2-normalise, MFMA top-candidates, exact fp32 refine, ratio test) on whole
 grids with validity masks; indices are GRID indices (the reference compacts with a boolean mask, which preserves order, so the
-correspondences are the same and nothing has to be synchronised to size a compacted tensor).  Everything else in this module is
-few-line device-tensor plumbing with the reference's names, signatures and return values."""
+correspondences are the same and nothing has to be synchronised to size a compacted tensor).  The ScanNet pairs' depth path
+(render_scannet_correspondence.py, correspondence.py:147-232) puts mvp_pointcloud_sample in front of it: each view's depth map is
+back-projected, the dense features are sampled at the points' projections (zero-padded bilinear) straight into the channel-major
+map the search reads.  Everything else in this module is few-line device-tensor plumbing with the reference's names, signatures
+and return values."""
 from __future__ import annotations
 
 import numpy as np
@@ -307,3 +310,249 @@ class SyntheticNAVI(torch.utils.data.Dataset):
         return {"image_0": texture(obj_0, hit_0), "image_1": texture(obj_1, hit_1),
                 "xyz_grid_0": xyz_0.permute(2, 0, 1).float(), "xyz_grid_1": xyz_1.permute(2, 0, 1).float(),
                 "Rt_01": Rt.float(), "intrinsics_1": K}
+
+
+# ----------------------------------------------------------------------------------------------- ScanNet pairs: the depth path
+SCANNET_PX_THRESH = (1, 2, 5, 15, 25, 35, 50)
+SCANNET_M_THRESH = (0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.4, 0.5)
+SCANNET_RESULT_NAMES = ([f"2D Recall ({t}px)" for t in SCANNET_PX_THRESH] + [f"3D Recall ({t}m)" for t in SCANNET_M_THRESH]
+                        + ["Bin Rec 0-30°", "Bin Rec 30-60°", "Bin Rec 60-90°", "Bin Rec 90-120°"])
+SCANNET_CSV_HEADER = ["Time", "Model Checkpoint", "Patch Size", "Layer", "Output", "Dataset", "Num Correspondences", "Scale Factor"] + SCANNET_RESULT_NAMES
+
+
+def grid_to_pointcloud(K_inv, depth, grid=None):
+    """correspondence.py:147-161: depth [1, H, W] -> [H * W, 3], the pixel centres back-projected by K_inv (row-major grid order; a
+    depth hole, value 0, becomes the point 0)."""
+    _, H, W = depth.shape
+    if grid is None:
+        grid = get_grid(H, W).to(depth)
+    points = (depth * grid).reshape(3, H * W)
+    return (K_inv.to(depth) @ points).permute(1, 0)
+
+
+def _pointcloud_sample(feats, K, pc, image_shape, want_valid=False):
+    """mvp_pointcloud_sample -> (out [C, N] fp32, valid uint8 [N] or None), on the device, no sync."""
+    _need_cuda(feats, pc)
+    H, W = (int(v) for v in image_shape)
+    f = feats.detach().contiguous().float()
+    p = pc.detach().contiguous().float()
+    if f.dim() != 3 or p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"expected feats [C, fh, fw] and pc [N, 3], got {tuple(f.shape)} and {tuple(p.shape)}")
+    Kd = K.detach().to(device=f.device, dtype=torch.float32).contiguous()
+    C, fh, fw = f.shape
+    N = p.shape[0]
+    out = torch.empty(C, N, dtype=torch.float32, device=f.device)
+    valid = torch.empty(N, dtype=torch.uint8, device=f.device) if want_valid else None
+    ops.pointcloud_sample(f, p, Kd, out, valid, C, fh, fw, N, H, W, N)
+    return out, valid
+
+
+def sample_pointcloud_features(feats, K, pc, image_shape):
+    """correspondence.py:164-176: feats [C, fh, fw], pc [N, 3], image_shape (H, W) of the grid K projects into -> [N, C], the
+    zero-padded bilinear samples at the points' projections (the .t() view of the kernel's channel-major [C, N] output).  The
+    arguments are not modified (the reference normalises uv in place, on its own temporary)."""
+    return _pointcloud_sample(feats, K, pc, image_shape)[0].t()
+
+
+def match_depth(feat_0, feat_1, depth_0, depth_1, K, num_corr=500, K_inv=None):
+    """The body of estimate_correspondence_depth (correspondence.py:218-232) on whole grids, without a host sync when K is a host
+    tensor (its inverse is then taken on the host, as the reference does) or when K_inv is given.  Returns a dict of device tensors
+    of the STATIC length k = min(num_corr, H * W): idx0 / idx1 (GRID indices, int64; the reference's compaction by z > 0 preserves
+    order, so the correspondences are the same), xyz0 / xyz1 [k, 3], dist [k] (the weights, sorted descending) and count (0-d
+    int64) = min(num_corr, valid cells of view 0); entries from ``count`` on are padding (weight -inf)."""
+    _need_cuda(feat_0, feat_1, depth_0, depth_1)
+    if K_inv is None:
+        K_inv = K.detach().cpu().inverse()  # a device K costs one sync here
+    xyz_0 = grid_to_pointcloud(K_inv, depth_0.float()).contiguous()
+    xyz_1 = grid_to_pointcloud(K_inv, depth_1.float()).contiguous()
+    f0, valid_0 = _pointcloud_sample(feat_0, K, xyz_0, depth_0.shape[-2:], want_valid=True)
+    f1, valid_1 = _pointcloud_sample(feat_1, K, xyz_1, depth_1.shape[-2:], want_valid=True)
+    nn_idx, dist, weight, n_valid = knn_ratio(f0, f1, valid_0, valid_1)
+    k = min(int(num_corr), xyz_0.shape[0])
+    c_dist, idx0 = torch.topk(weight, k=k, dim=-1)
+    idx1 = nn_idx.long()[idx0].clamp(min=0)  # padding entries point at cell 0 (never reported: count)
+    nv = n_valid.long()
+    count = torch.where(nv[1] >= 2, nv[0].clamp(max=k), torch.zeros_like(nv[0]))
+    return {"idx0": idx0, "idx1": idx1, "xyz0": xyz_0[idx0], "xyz1": xyz_1[idx1], "dist": c_dist, "count": count}
+
+
+def estimate_correspondence_depth(feat_0, feat_1, depth_0, depth_1, K, num_corr=500):
+    """correspondence.py:218-232: feat_* [C, fh, fw], depth_* [1, H, W], K [3, 3] -> (corr_xyz0, corr_xyz1, corr_dist), each of
+    length min(num_corr, points of view 0 with z > 0), ordered by descending weight.  One host sync, to trim."""
+    m = match_depth(feat_0, feat_1, depth_0, depth_1, K, num_corr)
+    n = int(m["count"])
+    return m["xyz0"][:n], m["xyz1"][:n], m["dist"][:n]
+
+
+def error_auc(errors, thresholds):
+    """correspondence.py:199-215 (host numpy): area under the recall-over-error curve up to each threshold, over the threshold."""
+    errors = [0] + sorted(list(errors))
+    recall = list(np.linspace(0, 1, len(errors)))
+    trapezoid = getattr(np, "trapezoid", None) or np.trapz
+    aucs = []
+    for thr in thresholds:
+        last_index = np.searchsorted(errors, thr)
+        y = recall[:last_index] + [recall[last_index - 1]]
+        x = errors[:last_index] + [thr]
+        aucs.append(trapezoid(y, x) / thr)
+    return aucs
+
+
+def evaluate_scannet(model, dataset, num_corr, scale_factor, multilayer, rank: int = 0, world: int = 1):
+    """render_scannet_correspondence.py:188-274 over EVERY pair -> the 19 numbers of ``SCANNET_RESULT_NAMES`` (Python floats; recalls
+    in %, an empty angle bin is nan).  One forward per pair on the stacked [rgb_0, rgb_1] (the reference's batch of 2: a wrapper
+    whose tap BN runs in train mode sees both views together), kept in flight by mvp.pipeline; depths resized by ``scale_factor``
+    (nearest), K[:2] scaled and inverted on the host; the matching stays on the device and the error vectors are fetched once at
+    the end.  With world > 1 the pairs are sharded (mvp.spair.shard_pairs) and gathered with one all_gather_object."""
+    import os
+
+    from .pipeline import pipelined_features
+    from .spair import shard_pairs
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mine = shard_pairs(len(dataset), rank, world)
+
+    def forwards():
+        for i in mine:
+            it = dataset[i]
+            rgbs = torch.stack((it["rgb_0"], it["rgb_1"]), dim=0).float().to(dev, non_blocking=True)
+            yield {"image": rgbs, "meta": (i, it)}
+
+    graphs = True if (world > 1 and os.environ.get("MVP_PIPELINE_GRAPHS") is None) else None  # no collective in flight in this loop (mvp/spair.py)
+    pending = []
+    for item, feats in pipelined_features(model, forwards(), graphs=graphs):
+        f = torch.cat(list(feats), dim=1) if isinstance(feats, (list, tuple)) else feats.clone()  # a copy: the slot's buffer is reused
+        i, it = item["meta"]
+        deps = torch.stack((it["depth_0"], it["depth_1"]), dim=0).float().to(dev, non_blocking=True)
+        deps = MF.interpolate(deps, scale_factor=scale_factor, mode="nearest")
+        K_host = it["K"].clone().float()
+        K_host[:2, :] *= scale_factor
+        K_mat, K_inv = K_host.to(dev), K_host.inverse().to(dev)
+        Rt = it["Rt_1"].float()[:3, :4].to(dev)
+        m = match_depth(f[0], f[1], deps[0], deps[1], K_mat, num_corr, K_inv=K_inv)
+        xyz0in1 = transform_points_Rt(m["xyz0"], Rt)
+        err3d = (xyz0in1 - m["xyz1"]).norm(p=2, dim=1)
+        err2d = (project_3dto2d(xyz0in1, K_mat) - project_3dto2d(m["xyz1"], K_mat)).norm(p=2, dim=1)
+        pending.append((i, err3d, err2d, m["count"], it["Rt_1"].float()[:3, :3]))
+    outs = [(i, e3[:int(c)].cpu(), e2[:int(c)].cpu(), R) for i, e3, e2, c, R in pending]  # the loop's only syncs
+    if world > 1:
+        import torch.distributed as dist
+
+        gathered = [None] * world
+        dist.all_gather_object(gathered, outs)
+        outs = sorted((o for part in gathered for o in part), key=lambda o: o[0])  # dataset order, as the reference's single loop
+    return summarize_scannet([o[1] for o in outs], [o[2] for o in outs], torch.stack([o[3] for o in outs]))
+
+
+def summarize_scannet(err_3d, err_2d, R_gt):
+    """render_scannet_correspondence.py:248-274 from per-pair error vectors (concatenated, as ``summarize`` does: the reference stacks
+    them, which needs equal lengths) and R_gt [n, 3, 3]: 2-D recalls, 3-D recalls, then the 2 cm recall per relative-angle bin."""
+    all3, all2 = torch.cat(err_3d).float(), torch.cat(err_2d).float()
+    out = [100.0 * (all2 < th).double().mean().item() for th in SCANNET_PX_THRESH]
+    out += [100.0 * (all3 < th).double().mean().item() for th in SCANNET_M_THRESH]
+    rel_ang = so3_rotation_angle(R_gt) * 180.0 / np.pi
+    rec_2cm = torch.stack([(e < 0.02).double().mean() for e in err_3d])
+    out += [float(v) * 100.0 for v in compute_binned_performance(rec_2cm, rel_ang, [0, 30, 60, 90, 120])]
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- synthetic ScanNet-shaped pairs
+class SyntheticScanNetPairs(torch.utils.data.Dataset):
+    """ScanNet-pairs-shaped instances (the keys of the reference's ScanNetPairsDataset.__getitem__): uid, class_id, sequence_id,
+    frame_0, frame_1, K [3, 3], rgb_0 / rgb_1 [3, H, W], depth_0 / depth_1 [1, H, W] (metres along the optical axis, 0 = no
+    reading), Rt_0 (identity) and Rt_1 [4, 4] (camera 0 -> camera 1).  The scene is the inside of a textured axis-aligned box room
+    (camera 0 stands in it with a yaw and a slight tilt); both cameras are ray-cast analytically at the pixel centres (slab test
+    from the inside), so depth and pose are exact by construction.  fx != fy and the principal point is off-centre; the relative
+    rotation is 15, 45 or 75 degrees (+- 10, cycling with the index) about a nearly vertical axis through a point in front of
+    camera 0, so the translation grows with it and the views keep common walls.  Depth holes, as a ScanNet sensor gives them: two
+    rectangles per view and everything beyond ``max_range``."""
+
+    name = "synthetic_scannet"
+    max_range = 2.6
+
+    def __init__(self, num_pairs=8, image_height=480, image_width=640, seed=0):
+        self.n, self.H, self.W, self.seed = int(num_pairs), int(image_height), int(image_width), int(seed)
+
+    def __len__(self):
+        return self.n
+
+    def intrinsics(self):
+        H, W = self.H, self.W
+        return torch.tensor([[0.90 * W, 0, 0.5 * W + 0.031 * W], [0, 0.93 * W, 0.5 * H - 0.027 * H], [0, 0, 1]], dtype=torch.float64)
+
+    @staticmethod
+    def _rodrigues(axis, angle):
+        axis = axis / axis.norm()
+        Kx = torch.tensor([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]], dtype=torch.float64)
+        return torch.eye(3, dtype=torch.float64) + np.sin(angle) * Kx + (1 - np.cos(angle)) * (Kx @ Kx)
+
+    def _scene(self, i):
+        """(generator, box lo / hi [3] in the room frame, room -> camera rotations R0 / R1, camera centres c0 / c1 in the room frame,
+        R and t of camera 0 -> camera 1) of pair i (float64)."""
+        g = torch.Generator().manual_seed(self.seed * 7919 + int(i))
+        r = lambda *shape: torch.rand(*shape, generator=g, dtype=torch.float64)  # noqa: E731
+        lo = -torch.tensor([1.3, 1.0, 1.2], dtype=torch.float64) - 0.4 * r(3)
+        hi = torch.tensor([1.5, 1.1, 1.9], dtype=torch.float64) + 0.4 * r(3)
+        up = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64)
+        R0 = self._rodrigues(up + 0.3 * (r(3) - 0.5), np.deg2rad(70.0 * (r(1).item() - 0.5)))  # camera 0: a yaw, slightly tilted
+        c0 = (r(3) - 0.5) * torch.tensor([0.8, 0.3, 0.8], dtype=torch.float64)
+        angle = np.deg2rad(15.0 + 30.0 * (int(i) % 3) + 20.0 * (r(1).item() - 0.5))
+        R = self._rodrigues((up + 0.15 * (r(3) - 0.5)) * (1.0 if r(1).item() < 0.5 else -1.0), angle)
+        R1 = R @ R0
+        # camera 1 swings about a point 1.2 m in front of camera 0 (so that a large rotation still leaves common walls), kept inside the room
+        pivot = c0 + 1.2 * R0[2]
+        c1 = pivot - (0.9 + 0.3 * r(1).item()) * R1[2] + (r(3) - 0.5) * torch.tensor([0.2, 0.1, 0.2], dtype=torch.float64)
+        c1 = torch.minimum(torch.maximum(c1, lo + 0.3), hi - 0.3)
+        return g, lo, hi, R0, R1, c0, c1, R, R1 @ (c0 - c1)
+
+    def _cast(self, R, centre, lo, hi):
+        """Pixel-centre rays of a camera (room -> camera rotation R, centre in the room frame) against the box from the inside:
+        camera-frame xyz [H, W, 3], room-frame hit points [H, W, 3] and the wall id (2 * axis + (1 if the high wall)) [H, W]."""
+        H, W = self.H, self.W
+        K = self.intrinsics()
+        u = ((torch.arange(W, dtype=torch.float64) + 0.5 - K[0, 2]) / K[0, 0]).view(1, W).expand(H, W)
+        v = ((torch.arange(H, dtype=torch.float64) + 0.5 - K[1, 2]) / K[1, 1]).view(H, 1).expand(H, W)
+        d_cam = torch.stack((u, v, torch.ones(H, W, dtype=torch.float64)), dim=-1)
+        d = d_cam @ R  # room frame: R^T d_cam
+        plane = torch.where(d > 0, hi.expand_as(d), lo.expand_as(d))
+        t_axis = torch.where(d != 0, (plane - centre) / torch.where(d != 0, d, torch.ones_like(d)), torch.full_like(d, float("inf")))
+        t, axis = t_axis.min(dim=-1)
+        wall = 2 * axis + (torch.gather(d, -1, axis[..., None])[..., 0] > 0).long()
+        return d_cam * t[..., None], centre + d * t[..., None], wall
+
+    def geometry(self, i):
+        """The scene behind pair i, without holes (tests): box lo / hi, the room -> camera rotations R_v and centres centre_v, R and t
+        of Rt_1, and per view v the camera-frame points xyz_v [H, W, 3], the room-frame hits room_v and the wall ids wall_v."""
+        _, lo, hi, R0, R1, c0, c1, R, t = self._scene(i)
+        x0, r0, w0 = self._cast(R0, c0, lo, hi)
+        x1, r1, w1 = self._cast(R1, c1, lo, hi)
+        return {"lo": lo, "hi": hi, "R": R, "t": t, "R_0": R0, "R_1": R1, "centre_0": c0, "centre_1": c1, "xyz_0": x0, "xyz_1": x1,
+                "room_0": r0, "room_1": r1, "wall_0": w0, "wall_1": w1}
+
+    def __getitem__(self, i):
+        g = self._scene(i)[0]
+        geo = self.geometry(i)
+        H, W = self.H, self.W
+        r = lambda *shape: torch.rand(*shape, generator=g, dtype=torch.float64)  # noqa: E731
+        # texture: a few random plane waves of the room-frame position, a different mix per wall
+        freq = (r(6, 3) - 0.5) * 2 * 14.0
+        phase = r(6, 3) * 2 * np.pi
+        amp = r(6, 3) + 0.2
+        wall_gain = 0.5 + r(6, 3)
+        out = {"uid": int(i), "class_id": "ScanNet_synthetic", "sequence_id": f"room{self.seed:04d}_{int(i):02d}", "frame_0": 0, "frame_1": 1,
+               "K": self.intrinsics().float()}
+        for v in (0, 1):
+            room, wall = geo[f"room_{v}"], geo[f"wall_{v}"]
+            img = (amp[None, None] * torch.sin((room @ freq.t())[..., None] + phase[None, None])).sum(-2) * wall_gain[wall] / 3.0
+            depth = geo[f"xyz_{v}"][..., 2].clone()
+            depth[depth > self.max_range] = 0.0
+            for _ in range(2):
+                hh, ww = int(H * (0.08 + 0.12 * r(1).item())), int(W * (0.08 + 0.12 * r(1).item()))
+                y0, x0 = int((H - hh) * r(1).item()), int((W - ww) * r(1).item())
+                depth[y0:y0 + hh, x0:x0 + ww] = 0.0
+            out[f"rgb_{v}"] = img.permute(2, 0, 1).float().clamp(-1, 1)
+            out[f"depth_{v}"] = depth[None].float()
+        Rt = torch.eye(4, dtype=torch.float64)
+        Rt[:3, :3], Rt[:3, 3] = geo["R"], geo["t"]
+        out["Rt_0"], out["Rt_1"] = torch.eye(4).float(), Rt.float()
+        return out

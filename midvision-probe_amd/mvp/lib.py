@@ -180,6 +180,11 @@ class KnnRatioArgs(C.Structure):  # mvp_knn_ratio_args: top-2 cosine nearest nei
                 ("n_valid", _vp), ("workspace", _vp), ("workspace_bytes", _i64), ("C", _i), ("N0", _i), ("N1", _i)]
 
 
+class PointcloudSampleArgs(C.Structure):  # mvp_pointcloud_sample_args: zero-padded bilinear sampling at projected points (added within ABI 8)
+    _fields_ = [("feat", _vp), ("pc", _vp), ("K", _vp), ("out", _vp), ("valid", _vp), ("C", _i), ("fh", _i), ("fw", _i), ("N", _i),
+                ("H", _i), ("W", _i), ("ld_out", _i)]
+
+
 class BnActArgs(C.Structure):  # mvp_bn_act_args: BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -329,6 +334,7 @@ SYMBOLS = {
     "mvp_bn_act_bwd": BnActArgs,
     "mvp_bce_loss_fwd_bwd": BceLossArgs,
     "mvp_binary_counts": BinaryCountsArgs,
+    "mvp_pointcloud_sample": PointcloudSampleArgs,
 }
 
 # the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
@@ -338,7 +344,7 @@ NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2d
                     "mvp_gather_rows_args": GatherRowsArgs, "mvp_relpos_terms_args": RelposTermsArgs,
                     "mvp_attention_relpos_args": AttentionRelposArgs, "mvp_knn_ratio_args": KnnRatioArgs,
                     "mvp_bn_act_args": BnActArgs, "mvp_bce_loss_args": BceLossArgs,
-                    "mvp_binary_counts_args": BinaryCountsArgs}  # the same for the additions of / within ABI 8
+                    "mvp_binary_counts_args": BinaryCountsArgs, "mvp_pointcloud_sample_args": PointcloudSampleArgs}  # the same for the additions of / within ABI 8
 
 _lib: Optional[C.CDLL] = None
 

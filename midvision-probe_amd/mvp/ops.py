@@ -499,6 +499,12 @@ def knn_ratio(src_feat, tgt_feat, src_valid, tgt_valid, nn_idx, dist, weight, n_
     lib.call("mvp_knn_ratio", a)
 
 
+def pointcloud_sample(feat, pc, K, out, valid, Cdim, fh, fw, N, H, W, ld_out) -> None:
+    """Zero-padded bilinear samples of feat [C, fh, fw] at the projections of pc [N, 3] -> out [C, ld_out] (include/mvp_hip.h)."""
+    a = lib.PointcloudSampleArgs(lib.ptr(feat), lib.ptr(pc), lib.ptr(K), lib.ptr(out), lib.ptr(valid), Cdim, fh, fw, N, H, W, ld_out)
+    lib.call("mvp_pointcloud_sample", a)
+
+
 def bn_act_workspace(device) -> torch.Tensor:
     """A workspace for bn_act_fwd / bn_act_bwd (MVP_BN_ACT_WORKSPACE_BYTES of fp64 partials)."""
     return torch.empty(lib.BN_ACT_WORKSPACE_BYTES // 8, dtype=torch.float64, device=device)
