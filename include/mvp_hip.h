@@ -536,7 +536,9 @@ int mvp_pack_nchw_tokens(const mvp_pack_nchw_args*, void* stream);
 typedef struct {
   const float* src; float* dst;
   int planes, Hi, Wi, Ho, Wo;
-  int mode; int align_corners;
+  int mode; int align_corners; /* align_corners belongs to bilinear / bicubic.  Callers pass 0 with MVP_RESIZE_NEAREST: torch has no such
+                                * form (F.interpolate raises ValueError, and so does mvp.functional.interpolate); a kernel given 1 would
+                                * take (in - 1) / (out - 1) as the nearest scale, which matches nothing in torch. */
   int channels_last; int C; /* C used only when channels_last */
   float scale_h, scale_w;   /* >0: the scale_factor given by the caller (recompute_scale_factor=False semantics); 0: derive from sizes */
 } mvp_resize_args;

@@ -51,6 +51,8 @@ def interpolate(x: torch.Tensor, size=None, scale_factor=None, mode: str = "near
     """Drop-in for torch.nn.functional.interpolate on NCHW fp32 (the modes the reference uses)."""
     if mode not in _MODES:
         raise NotImplementedError(f"interpolate mode {mode!r}")
+    if mode == "nearest" and align_corners is not None:  # as torch; the kernel's align_corners scale is not a nearest form
+        raise ValueError("align_corners option can only be set with the interpolating modes: bilinear | bicubic")
     Hi, Wi = x.shape[-2:]
     sh = sw = 0.0
     if size is not None:
