@@ -87,6 +87,9 @@ typedef struct {
                                 argument structs, no existing struct changed.
                                 Added within 8: mvp_pointcloud_sample (zero-padded bilinear sampling of a feature map at the projections of a point
                                 cloud, ScanNet pair correspondence); a new export with its own tagged argument struct, no existing struct changed.
+                                Added within 8: mvp_twoafc_score and mvp_twoafc_workspace_bytes (pooled cosine scoring of 2AFC triplets with the
+                                running confusion counts, the perceptual-similarity evaluation); new exports with their own tagged argument struct,
+                                no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -780,6 +783,47 @@ struct mvp_binary_counts_args {
   float threshold;
 };
 int mvp_binary_counts(const mvp_binary_counts_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; new exports with their own tagged argument struct, no existing struct changed.)
+ * Scoring of a batch of 2AFC triplets, the perceptual-similarity evaluation (evaluate_model_percepture.py:104-120: global average
+ * pool of CNN maps, two F.cosine_similarity, torch.where) with the running confusion counts.  For triplet b, x in {ref, left, right}
+ * points at B images of [C, HW] fp32, image b starting at element b * ld (the three parts of one stacked [3B, C, h, w] forward output
+ * are passed as three pointers; they may alias).  HW = 1: [B, C] class tokens.  Definition:
+ *     f_x[c]  = mean over HW of x[b, c, :]                                    (HW = 1: the value itself)
+ *     sim(x)  = <f_ref, f_x> / (max(|f_ref|, 1e-8) * max(|f_x|, 1e-8))        (F.cosine_similarity: each norm is clamped)
+ *     sim[b]  = {sim(left), sim(right)},   pred[b] = sim(left) > sim(right) ? 0 : 1     (compared as written, in fp32; NaN gives 1)
+ *     counts  = TP, FP, FN, TN of pred against label with positive = 1; a label that is neither 0 nor 1 is counted nowhere
+ * The pooled sums, both dot products, the three squared norms, the square roots and the division are fp64; each similarity is rounded
+ * once to fp32: |sim - exact| < 2^-24 for every finite input (no sum of squares of fp32 values overflows fp64, so features near 1e20,
+ * whose fp32 norms are inf, are scored like any others).  Both similarities of a triplet come from the same instruction sequence: bitwise-equal left and right give bitwise-equal similarities, hence pred = 1.
+ * counts is written only when label is given: overwritten when accumulate == 0, added to otherwise (a loop over batches keeps its
+ * running counts on the device without a launch of its own).
+ * How: a grid over (triplet, chunk of channels) streams the three images once, lanes along HW inside a channel row (16-byte loads when
+ * HW % 4 == 0, ld % 4 == 0 and the bases are 16-byte aligned, dword loads otherwise), and writes five fp64 partials per chunk; one wave
+ * per triplet folds them in a fixed order.  No floating-point atomics (the counts are integers), no sync, no allocation; two calls
+ * give the same bits.  Elements C * HW .. ld - 1 of an image are never read.
+ * MVP_EINVAL: NULL ref / left / right / sim / pred; counts without label; B, C or HW <= 0; ld < C * HW; C * HW > 2^31 - 1;
+ * B * chunks > 2^31 - 1 (chunks <= 256); workspace NULL, not 8-byte aligned or shorter than mvp_twoafc_workspace_bytes(B, C, HW);
+ * counts not 8-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_twoafc_args mvp_twoafc_args;
+struct mvp_twoafc_args {
+  const float* ref; const float* left; const float* right; /* image b of each at element b * ld, [C, HW] fp32                */
+  const float* label;                                      /* optional [B] fp32, exactly 0 or 1                              */
+  float* sim;                                              /* [B, 2]  sim(left), sim(right)                                  */
+  int32_t* pred;                                           /* [B]     0 = left is the closer one, 1 = right                  */
+  int64_t* counts;                                         /* optional [4] TP, FP, FN, TN; needs label                       */
+  void* workspace; int64_t workspace_bytes;                /* >= mvp_twoafc_workspace_bytes(B, C, HW), 8-byte aligned        */
+  int64_t ld;                                              /* elements between consecutive images, >= C * HW                 */
+  int B, C, HW;
+  int accumulate;                                          /* != 0: add to counts instead of overwriting them                */
+};
+/* Workspace: B * chunks * 40 bytes, chunks = ceil(C / ceil(C / min(256, ceil(C / ceil(4096 / HW))))): the most a launch uses (it
+ * rounds the channels of a chunk up to what a workgroup holds at once, which depends on the alignment).  0 for sizes that
+ * mvp_twoafc_score rejects. */
+int64_t mvp_twoafc_workspace_bytes(int B, int C, int HW);
+int mvp_twoafc_score(const mvp_twoafc_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution weight re-layout (per step; the probe's conv weights are trained):

@@ -185,6 +185,11 @@ class PointcloudSampleArgs(C.Structure):  # mvp_pointcloud_sample_args: zero-pad
                 ("H", _i), ("W", _i), ("ld_out", _i)]
 
 
+class TwoafcArgs(C.Structure):  # mvp_twoafc_args: pooled cosine scoring of 2AFC triplets + running confusion counts (added within ABI 8)
+    _fields_ = [("ref", _vp), ("left", _vp), ("right", _vp), ("label", _vp), ("sim", _vp), ("pred", _vp), ("counts", _vp),
+                ("workspace", _vp), ("workspace_bytes", _i64), ("ld", _i64), ("B", _i), ("C", _i), ("HW", _i), ("accumulate", _i)]
+
+
 class BnActArgs(C.Structure):  # mvp_bn_act_args: BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -335,6 +340,8 @@ SYMBOLS = {
     "mvp_bce_loss_fwd_bwd": BceLossArgs,
     "mvp_binary_counts": BinaryCountsArgs,
     "mvp_pointcloud_sample": PointcloudSampleArgs,
+    "mvp_twoafc_score": TwoafcArgs,
+    "mvp_twoafc_workspace_bytes": None,
 }
 
 # the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
@@ -344,7 +351,8 @@ NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2d
                     "mvp_gather_rows_args": GatherRowsArgs, "mvp_relpos_terms_args": RelposTermsArgs,
                     "mvp_attention_relpos_args": AttentionRelposArgs, "mvp_knn_ratio_args": KnnRatioArgs,
                     "mvp_bn_act_args": BnActArgs, "mvp_bce_loss_args": BceLossArgs,
-                    "mvp_binary_counts_args": BinaryCountsArgs, "mvp_pointcloud_sample_args": PointcloudSampleArgs}  # the same for the additions of / within ABI 8
+                    "mvp_binary_counts_args": BinaryCountsArgs, "mvp_pointcloud_sample_args": PointcloudSampleArgs,
+                    "mvp_twoafc_args": TwoafcArgs}  # the same for the additions of / within ABI 8
 
 _lib: Optional[C.CDLL] = None
 
@@ -375,6 +383,8 @@ def load() -> C.CDLL:
     lib.mvp_corr_workspace_bytes.restype = _i64
     lib.mvp_knn_workspace_bytes.argtypes = [_i, _i, _i]
     lib.mvp_knn_workspace_bytes.restype = _i64
+    lib.mvp_twoafc_workspace_bytes.argtypes = [_i, _i, _i]
+    lib.mvp_twoafc_workspace_bytes.restype = _i64
     lib.mvp_sizeof.argtypes = [C.c_char_p]
     lib.mvp_sizeof.restype = _i
     lib.mvp_bn_tokens_workspace_bytes.argtypes = [_i, _i]

@@ -505,6 +505,18 @@ def pointcloud_sample(feat, pc, K, out, valid, Cdim, fh, fw, N, H, W, ld_out) ->
     lib.call("mvp_pointcloud_sample", a)
 
 
+def twoafc_workspace_bytes(B: int, Cdim: int, HW: int) -> int:
+    return int(lib.load().mvp_twoafc_workspace_bytes(B, Cdim, HW))
+
+
+def twoafc_score(ref, left, right, sim, pred, workspace, B, Cdim, HW, ld, label=None, counts=None, accumulate=False) -> None:
+    """sim [B, 2] / pred [B] int32 of B triplets of [C, HW] fp32 images ld elements apart, and (with label [B]) the TP / FP / FN / TN in
+    counts [4] int64, overwritten or added to (include/mvp_hip.h: mvp_twoafc_score).  ref / left / right may be slices of one tensor."""
+    a = lib.TwoafcArgs(lib.ptr(ref), lib.ptr(left), lib.ptr(right), lib.ptr(label), lib.ptr(sim), lib.ptr(pred), lib.ptr(counts),
+                       lib.ptr(workspace), workspace.numel() * workspace.element_size(), ld, B, Cdim, HW, int(accumulate))
+    _traced("hbm", "twoafc_score", 0, float(3 * B * Cdim * HW * 4), lambda: lib.call("mvp_twoafc_score", a))
+
+
 def bn_act_workspace(device) -> torch.Tensor:
     """A workspace for bn_act_fwd / bn_act_bwd (MVP_BN_ACT_WORKSPACE_BYTES of fp64 partials)."""
     return torch.empty(lib.BN_ACT_WORKSPACE_BYTES // 8, dtype=torch.float64, device=device)
