@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import evalloop
 from . import functional as MF
 from . import lib, ops
 
@@ -136,6 +137,17 @@ def so3_relative_angle(R1: torch.Tensor, R2: torch.Tensor, eps: float = 1e-4):
 
 
 # ----------------------------------------------------------------------------------------------- one pair, on the device
+def _select(weight, nn_idx, n_valid, num_corr):
+    """The selection both match_* functions end in: (weights [k] sorted descending, idx0, idx1, count) of the k = min(num_corr, queries)
+    heaviest queries (a STATIC length); count (0-d int64) = min(k, valid queries), 0 with fewer than two valid candidates."""
+    k = min(int(num_corr), weight.shape[0])
+    c_dist, idx0 = torch.topk(weight, k=k, dim=-1)
+    idx1 = nn_idx.long()[idx0].clamp(min=0)  # padding entries point at cell 0 (never reported: count)
+    nv = n_valid.long()
+    count = torch.where(nv[1] >= 2, nv[0].clamp(max=k), torch.zeros_like(nv[0]))
+    return c_dist, idx0, idx1, count
+
+
 def match_grids(feat_0, feat_1, xyz_grid_0, xyz_grid_1, num_corr=500, ratio_test=True):
     """The body of estimate_correspondence_xyz (correspondence.py:235-263) without a host sync.  Returns a dict of device tensors of
     the STATIC length k = min(num_corr, h * w): idx0 / idx1 (grid indices, int64), xyz0 / xyz1 [k, 3], dist [k] (the weights, sorted
@@ -150,14 +162,10 @@ def match_grids(feat_0, feat_1, xyz_grid_0, xyz_grid_1, num_corr=500, ratio_test
     nn_idx, dist, weight, n_valid = knn_ratio(up0, up1, valid_0, valid_1)
     if not ratio_test:
         weight = torch.where(nn_idx >= 0, dist[:, 0], weight)  # invalid queries keep -inf
-    k = min(int(num_corr), h * w)
-    c_dist, idx0 = torch.topk(weight, k=k, dim=-1)
-    idx1 = nn_idx.long()[idx0].clamp(min=0)  # padding entries point at cell 0 (never reported: count)
+    c_dist, idx0, idx1, count = _select(weight, nn_idx, n_valid, num_corr)
     uvd = get_grid(h, w).to(xyz_grid_0).permute(1, 2, 0).reshape(h * w, 3)
     xyz_0 = xyz_grid_0.permute(1, 2, 0).reshape(h * w, 3)
     xyz_1 = xyz_grid_1.permute(1, 2, 0).reshape(h * w, 3)
-    nv = n_valid.long()
-    count = torch.where(nv[1] >= 2, nv[0].clamp(max=k), torch.zeros_like(nv[0]))
     return {"idx0": idx0, "idx1": idx1, "xyz0": xyz_0[idx0], "xyz1": xyz_1[idx1], "dist": c_dist, "uv0": uvd[idx0][:, :2],
             "uv1": uvd.to(xyz_grid_1)[idx1][:, :2], "count": count}
 
@@ -179,16 +187,13 @@ def evaluate_dataset(model, dataset, num_corr, scale_factor, multilayer, batch_s
     """evaluate_navi_correspondence.py:121-223 -> the ten numbers of ``RESULT_NAMES`` (Python floats; recalls in %, an empty angle bin
     is nan).  Loader batches of ``batch_size`` pairs in dataset order; per batch ``model(image_0)`` then ``model(image_1)``, two
     separate forwards kept in flight by mvp.pipeline (each equal, bit for bit, to the serial call); the per-pair matching stays on
-    the device and the error vectors are fetched once at the end.  With world > 1 the BATCHES are sharded (mvp.spair.shard_pairs over
-    batch indices: a wrapper whose train-mode tap BN couples the images of a forward then sees the same batches at any world size)
-    and gathered with one all_gather_object."""
-    from .pipeline import pipelined_features
-    from .spair import shard_pairs
-
+    the device and the error vectors are fetched once at the end.  With world > 1 the BATCHES are sharded (evalloop.shard over batch
+    indices: a wrapper whose train-mode tap BN couples the images of a forward then sees the same batches at any world size), the
+    rows gathered once and sorted by pair index."""
     dev = torch.device("cuda", torch.cuda.current_device())
     n = len(dataset)
     batches = [list(range(s, min(s + batch_size, n))) for s in range(0, n, batch_size)]
-    mine = shard_pairs(len(batches), rank, world)
+    mine = evalloop.shard(len(batches), rank, world)
 
     def forwards():
         for b in mine:
@@ -196,15 +201,11 @@ def evaluate_dataset(model, dataset, num_corr, scale_factor, multilayer, batch_s
             yield {"image": batch["image_0"].float(), "meta": (b, 0, batch)}
             yield {"image": batch["image_1"].float(), "meta": (b, 1, batch)}
 
-    import os
-
-    graphs = True if (world > 1 and os.environ.get("MVP_PIPELINE_GRAPHS") is None) else None  # no collective in flight in this loop (mvp/spair.py)
     pending, feat_0 = [], None
-    for item, feats in pipelined_features(model, forwards(), graphs=graphs):
-        f = torch.cat(list(feats), dim=1) if isinstance(feats, (list, tuple)) else feats.clone()  # a copy: the slot's buffer is reused
+    for item, f in evalloop.features(model, forwards(), world):
         b, view, batch = item["meta"]
         if view == 0:
-            feat_0 = f
+            feat_0 = f.clone()  # view 0 is kept across the next forward, which may reuse the buffer f is a view of
             continue
         xyz_0 = MF.interpolate(batch["xyz_grid_0"].float(), scale_factor=scale_factor, mode="nearest")
         xyz_1 = MF.interpolate(batch["xyz_grid_1"].float(), scale_factor=scale_factor, mode="nearest")
@@ -212,31 +213,45 @@ def evaluate_dataset(model, dataset, num_corr, scale_factor, multilayer, batch_s
         K = batch["intrinsics_1"].float()
         for j, i in enumerate(batches[b]):
             m = match_grids(feat_0[j], f[j], xyz_0[j], xyz_1[j], num_corr)
-            xyz0in1 = transform_points_Rt(m["xyz0"], Rt[j])
-            err3d = (xyz0in1 - m["xyz1"]).norm(p=2, dim=1)
-            err2d = (project_3dto2d(xyz0in1, K[j]) - project_3dto2d(m["xyz1"], K[j])).norm(p=2, dim=1)
-            pending.append((i, err3d, err2d, m["count"], Rt[j, :3, :3]))
-    outs = [(i, e3[:int(c)].cpu(), e2[:int(c)].cpu(), R.cpu()) for i, e3, e2, c, R in pending]  # the loop's only syncs
-    if world > 1:
-        import torch.distributed as dist
-
-        gathered = [None] * world
-        dist.all_gather_object(gathered, outs)
-        outs = sorted((o for part in gathered for o in part), key=lambda o: o[0])  # dataset order, as the reference's single loop
+            pending.append((i, *_pair_errors(m, Rt[j], K[j]), m["count"], Rt[j, :3, :3]))
+    outs = evalloop.in_index_order(evalloop.gather_parts(_fetch(pending), world))
     return summarize([o[1] for o in outs], [o[2] for o in outs], torch.stack([o[3] for o in outs]))
+
+
+def _pair_errors(m, Rt, K):
+    """(err3d, err2d), each [k], of a match dict: view 0's points moved into camera 1 by Rt [3, 4] against view 1's points, in metres
+    and, projected by K, in pixels.  On the device, no sync; entries from m["count"] on are padding."""
+    xyz0in1 = transform_points_Rt(m["xyz0"], Rt)
+    err3d = (xyz0in1 - m["xyz1"]).norm(p=2, dim=1)
+    err2d = (project_3dto2d(xyz0in1, K) - project_3dto2d(m["xyz1"], K)).norm(p=2, dim=1)
+    return err3d, err2d
+
+
+def _fetch(pending):
+    """Rows (pair index, err3d, err2d, count, R_gt) of a finished loop -> host rows with the errors trimmed to ``count``: the loop's
+    only host syncs, after its last forward has been issued.  (R_gt: a device slice for NAVI, already on the host for ScanNet.)"""
+    return [(i, e3[:int(c)].cpu(), e2[:int(c)].cpu(), R.cpu()) for i, e3, e2, c, R in pending]
+
+
+def _recalls(err, thresholds):
+    """Recall in % at each threshold (means of 0 / 1 in fp64: the reference's fp32 mean rounds count / n in the 7th digit; it prints
+    two decimals)."""
+    return [100.0 * (err < th).double().mean().item() for th in thresholds]
+
+
+def _angle_bin_recalls(err_3d, R_gt):
+    """The pairs' 2 cm recall in %, averaged per 30-degree bin of the relative rotation angle up to 120 (an empty bin is nan)."""
+    rel_ang = so3_rotation_angle(R_gt) * 180.0 / np.pi
+    rec_2cm = torch.stack([(e < 0.02).double().mean() for e in err_3d])
+    return [float(v) * 100.0 for v in compute_binned_performance(rec_2cm, rel_ang, [0, 30, 60, 90, 120])]
 
 
 def summarize(err_3d, err_2d, R_gt):
     """evaluate_navi_correspondence.py:196-223 from per-pair error vectors (the reference stacks them, which needs equal lengths;
-    here pairs with fewer than num_corr valid cells simply contribute fewer correspondences) and R_gt [n, 3, 3]."""
+    here pairs with fewer than num_corr valid cells simply contribute fewer correspondences) and R_gt [n, 3, 3]: 3-D recalls, 2-D
+    recalls, angle bins."""
     all3, all2 = torch.cat(err_3d).float(), torch.cat(err_2d).float()
-    # (means of 0 / 1 in fp64: the reference's fp32 mean rounds count / n in the 7th digit; it prints two decimals)
-    out = [100.0 * (all3 < th).double().mean().item() for th in (0.01, 0.02, 0.05)]
-    out += [100.0 * (all2 < th).double().mean().item() for th in (5, 25, 50)]
-    rel_ang = so3_rotation_angle(R_gt) * 180.0 / np.pi
-    rec_2cm = torch.stack([(e < 0.02).double().mean() for e in err_3d])
-    out += [float(v) * 100.0 for v in compute_binned_performance(rec_2cm, rel_ang, [0, 30, 60, 90, 120])]
-    return out
+    return _recalls(all3, (0.01, 0.02, 0.05)) + _recalls(all2, (5, 25, 50)) + _angle_bin_recalls(err_3d, R_gt)
 
 
 # ----------------------------------------------------------------------------------------------- synthetic NAVI-shaped pairs
@@ -368,11 +383,7 @@ def match_depth(feat_0, feat_1, depth_0, depth_1, K, num_corr=500, K_inv=None):
     f0, valid_0 = _pointcloud_sample(feat_0, K, xyz_0, depth_0.shape[-2:], want_valid=True)
     f1, valid_1 = _pointcloud_sample(feat_1, K, xyz_1, depth_1.shape[-2:], want_valid=True)
     nn_idx, dist, weight, n_valid = knn_ratio(f0, f1, valid_0, valid_1)
-    k = min(int(num_corr), xyz_0.shape[0])
-    c_dist, idx0 = torch.topk(weight, k=k, dim=-1)
-    idx1 = nn_idx.long()[idx0].clamp(min=0)  # padding entries point at cell 0 (never reported: count)
-    nv = n_valid.long()
-    count = torch.where(nv[1] >= 2, nv[0].clamp(max=k), torch.zeros_like(nv[0]))
+    c_dist, idx0, idx1, count = _select(weight, nn_idx, n_valid, num_corr)
     return {"idx0": idx0, "idx1": idx1, "xyz0": xyz_0[idx0], "xyz1": xyz_1[idx1], "dist": c_dist, "count": count}
 
 
@@ -403,14 +414,9 @@ def evaluate_scannet(model, dataset, num_corr, scale_factor, multilayer, rank: i
     in %, an empty angle bin is nan).  One forward per pair on the stacked [rgb_0, rgb_1] (the reference's batch of 2: a wrapper
     whose tap BN runs in train mode sees both views together), kept in flight by mvp.pipeline; depths resized by ``scale_factor``
     (nearest), K[:2] scaled and inverted on the host; the matching stays on the device and the error vectors are fetched once at
-    the end.  With world > 1 the pairs are sharded (mvp.spair.shard_pairs) and gathered with one all_gather_object."""
-    import os
-
-    from .pipeline import pipelined_features
-    from .spair import shard_pairs
-
+    the end.  With world > 1 the pairs are sharded (evalloop.shard) and the rows gathered once."""
     dev = torch.device("cuda", torch.cuda.current_device())
-    mine = shard_pairs(len(dataset), rank, world)
+    mine = evalloop.shard(len(dataset), rank, world)
 
     def forwards():
         for i in mine:
@@ -418,10 +424,9 @@ def evaluate_scannet(model, dataset, num_corr, scale_factor, multilayer, rank: i
             rgbs = torch.stack((it["rgb_0"], it["rgb_1"]), dim=0).float().to(dev, non_blocking=True)
             yield {"image": rgbs, "meta": (i, it)}
 
-    graphs = True if (world > 1 and os.environ.get("MVP_PIPELINE_GRAPHS") is None) else None  # no collective in flight in this loop (mvp/spair.py)
     pending = []
-    for item, feats in pipelined_features(model, forwards(), graphs=graphs):
-        f = torch.cat(list(feats), dim=1) if isinstance(feats, (list, tuple)) else feats.clone()  # a copy: the slot's buffer is reused
+    for item, f in evalloop.features(model, forwards(), world):
+        f = f.clone()  # the copy this loop has always made, kept so that nothing changes (SPair's, which consumes f the same way, has none)
         i, it = item["meta"]
         deps = torch.stack((it["depth_0"], it["depth_1"]), dim=0).float().to(dev, non_blocking=True)
         deps = MF.interpolate(deps, scale_factor=scale_factor, mode="nearest")
@@ -430,17 +435,8 @@ def evaluate_scannet(model, dataset, num_corr, scale_factor, multilayer, rank: i
         K_mat, K_inv = K_host.to(dev), K_host.inverse().to(dev)
         Rt = it["Rt_1"].float()[:3, :4].to(dev)
         m = match_depth(f[0], f[1], deps[0], deps[1], K_mat, num_corr, K_inv=K_inv)
-        xyz0in1 = transform_points_Rt(m["xyz0"], Rt)
-        err3d = (xyz0in1 - m["xyz1"]).norm(p=2, dim=1)
-        err2d = (project_3dto2d(xyz0in1, K_mat) - project_3dto2d(m["xyz1"], K_mat)).norm(p=2, dim=1)
-        pending.append((i, err3d, err2d, m["count"], it["Rt_1"].float()[:3, :3]))
-    outs = [(i, e3[:int(c)].cpu(), e2[:int(c)].cpu(), R) for i, e3, e2, c, R in pending]  # the loop's only syncs
-    if world > 1:
-        import torch.distributed as dist
-
-        gathered = [None] * world
-        dist.all_gather_object(gathered, outs)
-        outs = sorted((o for part in gathered for o in part), key=lambda o: o[0])  # dataset order, as the reference's single loop
+        pending.append((i, *_pair_errors(m, Rt, K_mat), m["count"], it["Rt_1"].float()[:3, :3]))
+    outs = evalloop.in_index_order(evalloop.gather_parts(_fetch(pending), world))
     return summarize_scannet([o[1] for o in outs], [o[2] for o in outs], torch.stack([o[3] for o in outs]))
 
 
@@ -448,12 +444,7 @@ def summarize_scannet(err_3d, err_2d, R_gt):
     """render_scannet_correspondence.py:248-274 from per-pair error vectors (concatenated, as ``summarize`` does: the reference stacks
     them, which needs equal lengths) and R_gt [n, 3, 3]: 2-D recalls, 3-D recalls, then the 2 cm recall per relative-angle bin."""
     all3, all2 = torch.cat(err_3d).float(), torch.cat(err_2d).float()
-    out = [100.0 * (all2 < th).double().mean().item() for th in SCANNET_PX_THRESH]
-    out += [100.0 * (all3 < th).double().mean().item() for th in SCANNET_M_THRESH]
-    rel_ang = so3_rotation_angle(R_gt) * 180.0 / np.pi
-    rec_2cm = torch.stack([(e < 0.02).double().mean() for e in err_3d])
-    out += [float(v) * 100.0 for v in compute_binned_performance(rec_2cm, rel_ang, [0, 30, 60, 90, 120])]
-    return out
+    return _recalls(all2, SCANNET_PX_THRESH) + _recalls(all3, SCANNET_M_THRESH) + _angle_bin_recalls(err_3d, R_gt)
 
 
 # ----------------------------------------------------------------------------------------------- synthetic ScanNet-shaped pairs

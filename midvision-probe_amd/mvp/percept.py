@@ -7,11 +7,13 @@ forward (class tokens as they are, CNN maps with the global average pool fused i
 confusion counts on the device: one device-to-host transfer per shard, after the loop."""
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import torch
 
 from . import lib, ops
+from .evalloop import PinnedRing, gather_parts
+from .evalloop import shard as shard_batches  # the same function: rank r takes loader batches r, r + W, ...
 
 METRIC_NAMES = ("accuracy", "f1_score", "precision", "recall")
 CSV_HEADER = ["Model Name", "Test Accuracy", "Test F1-Score", "Test Precision", "Test Recall"]
@@ -92,12 +94,6 @@ def compute_metrics(gt_labels, pred_labels) -> Dict[str, float]:
 
 
 # ----------------------------------------------------------------------------- sharding
-def shard_batches(n_batches: int, rank: int, world: int) -> List[int]:
-    """Rank r takes batches r, r + W, ...: every batch once, nothing padded (DistributedSampler would repeat samples, and a repeated
-    triplet changes the counts)."""
-    return list(range(rank, n_batches, world))
-
-
 def merge_shards(parts):
     """parts: per rank (rows, counts, errors), rows = [(batch index, [result dicts])].  -> (results in loader order, summed counts,
     errors)."""
@@ -157,20 +153,24 @@ def predict_batch(model, dataloader, output_dir, wandb_use=False, rank: int = 0,
     """Reference: evaluate_model_percepture.py:67-167 -> (results, metrics, errors); results = [{"id", "gt", "prediction"}] in loader
     order.  ``output_dir`` and ``wandb_use`` are accepted and unused (the reference's csv dump is commented out; no wandb here).
     With world > 1 every rank returns the merged result of all ranks."""
-    from .spair import _PinnedRing
-
     dev = torch.device("cuda", torch.cuda.current_device())
     model = model.to(dev)
     model.eval()
-    ring = _PinnedRing(4)
+    ring = PinnedRing(4)
     try:  # a shard's share of the triplets, rounded up by one batch
         capacity = -(-len(dataloader.dataset) // world) + (getattr(dataloader, "batch_size", None) or 1)
     except (TypeError, AttributeError):  # a plain iterable of batches: the log grows as needed
         capacity = _LOG_CAPACITY
     log = _DeviceLog(capacity, dev)
     rows, errors = [], []
-    for bi, batch in enumerate(dataloader):
-        if bi % world != rank:
+    try:
+        n_batches = len(dataloader)
+    except TypeError:  # a generator of batches, a loader over an iterable dataset: the shard is cut from the number of batches
+        dataloader = list(dataloader)
+        n_batches = len(dataloader)
+    mine = set(shard_batches(n_batches, rank, world))
+    for bi, batch in enumerate(dataloader):  # every rank walks the whole loader
+        if bi not in mine:
             continue
         try:  # the reference's blanket try / except, kept for what can go wrong BEFORE anything is launched
             img_ref, img_left, img_right, p, ids = batch
@@ -197,13 +197,7 @@ def predict_batch(model, dataloader, output_dir, wandb_use=False, rank: int = 0,
     for bi, id_list, gts in rows:
         out_rows.append((bi, [{"id": i, "gt": g, "prediction": int(pr)} for i, g, pr in zip(id_list, gts, preds[k:k + len(gts)])]))
         k += len(gts)
-    parts = [(out_rows, counts, errors)]
-    if world > 1:
-        import torch.distributed as dist
-
-        parts = [None] * world
-        dist.all_gather_object(parts, (out_rows, counts, errors))
-    results, counts, errors = merge_shards(parts)
+    results, counts, errors = merge_shards(gather_parts((out_rows, counts, errors), world))
     return results, metrics_from_counts(*counts), errors
 
 

@@ -8,7 +8,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import lib, ops
+from . import evalloop, lib, ops
+from .evalloop import shard as shard_pairs  # the same function: pairs are independent (tap BN couples only the two images of a pair)
 
 
 def argmax_2d(x: torch.Tensor, max_value: bool = True) -> torch.Tensor:
@@ -58,33 +59,7 @@ def compute_errors(model, instance, mask_feats=False, return_heatmaps=False):
     return out
 
 
-class _PinnedRing:
-    """Host -> device staging through a few reused pinned buffers: the copy engine moves them asynchronously, where a pageable
-    ``.to(device)`` blocks the host until the copy has run (and with it the whole look-ahead of the pipeline)."""
-
-    def __init__(self, slots: int):
-        self.slots, self.k = [dict() for _ in range(max(2, slots))], 0
-
-    def to_device(self, parts, dev, dtype=torch.float32) -> torch.Tensor:
-        """torch.stack(parts) on the device."""
-        slot = self.slots[self.k % len(self.slots)]
-        self.k += 1
-        shape = (len(parts),) + tuple(parts[0].shape)
-        ev = slot.get("event")
-        if ev is not None:
-            ev.synchronize()  # the copy that last read this pinned buffer has finished (normally long ago)
-        buf = slot.get("buf")
-        if buf is None or tuple(buf.shape) != shape or buf.dtype != dtype:
-            buf = slot["buf"] = torch.empty(shape, dtype=dtype).pin_memory()
-        torch.stack([p.to(dtype) for p in parts], out=buf)
-        out = torch.empty(shape, dtype=dtype, device=dev)
-        out.copy_(buf, non_blocking=True)
-        slot["event"] = torch.cuda.Event()
-        slot["event"].record()
-        return out
-
-
-def _pair_inputs(instance, ring: "_PinnedRing" = None):
+def _pair_inputs(instance, ring: evalloop.PinnedRing = None):
     """(images [2,3,S,S] on the device, kps_i, kps_j with (x, y) scaled to [0,1], thresh_scale): evaluate_spair_correspondence.py:47-60."""
     img_i, mask_i, kps_i, img_j, mask_j, kps_j, thresh_scale, _ = instance
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -110,23 +85,15 @@ def _pck_rows(pred_kp: torch.Tensor, kps_i: torch.Tensor, kps_j: torch.Tensor, t
     return error_same, error_nn, index_same, index_nn
 
 
-def shard_pairs(n_pairs: int, rank: int, world: int):
-    """Image pairs are independent (tap BN couples only the two images of a pair): rank r takes
-    pairs r, r+W, ...; per-pair error vectors are gathered at the end."""
-    return list(range(rank, n_pairs, world))
-
-
 def evaluate_dataset(model, dataset, thresh, verbose=False, rank: int = 0, world: int = 1):
     """Reference: evaluate_spair_correspondence.py:104-121 -> (recall in %, confusion matrix).  With world > 1 the pairs are sharded
-    (rank r takes pairs r, r + W, ...; pairs are independent) and the per-pair error / index vectors are gathered with
-    one all_gather_object at the end (host-side lists of a few floats per pair), so every rank returns the full-dataset result."""
+    (rank r takes pairs r, r + W, ...; pairs are independent) and the per-pair error / index vectors are gathered once
+    at the end (mvp/evalloop.py; host-side lists of a few floats per pair), so every rank returns the full-dataset result."""
     idx = shard_pairs(len(dataset), rank, world)
     # The pairs' forwards are kept in flight (mvp/pipeline.py; pairs are independent, the wrapper's train-mode tap BN sees one pair at a
     # time and its running statistics are updated in pair order), the correspondence kernel of pair t runs under the forwards of the
     # next pairs, and the predicted keypoints stay on the device until the end: one host sync per shard instead of one per pair.
-    from .pipeline import pipelined_features
-
-    ring = _PinnedRing(8)  # images and keypoints go through pinned staging: nothing in the loop blocks the host
+    ring = evalloop.PinnedRing(8)  # images and keypoints go through pinned staging: nothing in the loop blocks the host
 
     def pairs():
         for i in idx:
@@ -134,26 +101,13 @@ def evaluate_dataset(model, dataset, thresh, verbose=False, rank: int = 0, world
             kp_dev = ring.to_device((kps_i[:, :2].contiguous(),), images.device)[0]
             yield {"image": images, "meta": (i, kps_i, kps_j, thresh_scale, kp_dev)}
 
-    # Jobs with more than one rank launch their forwards eagerly by default (mvp/pipeline.py: a lazy graph capture is a device-wide sync
-    # that must not land beside a pending all-reduce).  This loop has NO collective in flight — the one exchange is the
-    # all_gather_object after it — so it keeps hipGraph replay at any world size (eager launches: 48-80 pairs/s against 115-148 at
-    # 800^2, profiles/r04_fullsize_configs.txt); MVP_PIPELINE_GRAPHS still wins when set.
-    import os
-
-    graphs = True if (world > 1 and os.environ.get("MVP_PIPELINE_GRAPHS") is None) else None
     pending = []
-    for b, feats in pipelined_features(model, pairs(), graphs=graphs):
-        f = torch.cat(list(feats), dim=1) if isinstance(feats, (list, tuple)) else feats
+    for b, f in evalloop.features(model, pairs(), world):  # (no copy of f: it is consumed before the next pair is taken)
         i, kps_i, kps_j, thresh_scale, kp_dev = b["meta"]
         pred_xy, _ = correspondence(f[0], f[1], kp_dev)
         pending.append((i, pred_xy, f.shape[-1], kps_i, kps_j, thresh_scale))
     outs = [(i,) + _pck_rows(pred_xy.float().cpu() / fw, kps_i, kps_j, ts) for i, pred_xy, fw, kps_i, kps_j, ts in pending]
-    if world > 1:
-        import torch.distributed as dist
-
-        gathered = [None] * world
-        dist.all_gather_object(gathered, outs)
-        outs = sorted((o for part in gathered for o in part), key=lambda o: o[0])  # dataset order, as the reference's single loop
+    outs = evalloop.in_index_order(evalloop.gather_parts(outs, world))
     errors = torch.cat([o[1] for o in outs])
     src_ind = torch.cat([o[3] for o in outs])
     tgt_ind = torch.cat([o[4] for o in outs])
