@@ -26,7 +26,8 @@ BN_ACT_NONE, BN_ACT_SIGMOID, BN_ACT_TANH = 0, 1, 2  # MVP_BN_ACT_*
 BN_ACT_WORKSPACE_BYTES, BCE_WORKSPACE_BYTES = 98304, 8192  # MVP_BN_ACT_WORKSPACE_BYTES, MVP_BCE_WORKSPACE_BYTES
 BN_RUNNING_MAX = 8  # MVP_BN_RUNNING_MAX: modules per mvp_bn_running_update_n launch
 TILES_SHARED, TILES_NO_PP, TILES_NO_UNI = 1, 2, 4
-ROUTE_PP, ROUTE_TILE, ROUTE_SPLITK, ROUTE_CONV = 1, 2, 3, 4  # mvp_gemm_route_t.family
+ROUTE_PP, ROUTE_TILE, ROUTE_SPLITK, ROUTE_CONV = 1, 2, 3, 4  # MVP_GEMM_ROUTE_*: mvp_gemm_route_t.family
+ATT_V_BF16_PAIR, ATT_V_F16, ATT_V_F16_QK_F16 = 0, 1, 2  # MVP_ATT_V_*: mvp_attention_args.v_format
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -38,20 +39,29 @@ class MvpError(RuntimeError):
     pass
 
 
-class Info(C.Structure):
+STRUCTS = {}  # C struct name in include/mvp_hip.h -> its ctypes mirror below; tests/test_abi.py holds each to the header field by field
+
+
+class Struct(C.Structure):
+    def __init_subclass__(cls, c_name: str, **kw):
+        super().__init_subclass__(**kw)
+        STRUCTS[c_name] = cls
+
+
+class Info(Struct, c_name="mvp_info_t"):
     _fields_ = [("abi_version", _i), ("device_count", _i), ("gfx950", _i), ("cu_count", _i), ("arch", C.c_char * 64)]
 
 
-class SplitArgs(C.Structure):
+class SplitArgs(Struct, c_name="mvp_split_bf16_args"):
     _fields_ = [("src", _vp), ("hi", _vp), ("lo", _vp), ("n", _i64)]
 
 
-class PatchGatherArgs(C.Structure):
+class PatchGatherArgs(Struct, c_name="mvp_patch_gather_args"):
     _fields_ = [("images", _vp), ("out_hi", _vp), ("out_lo", _vp), ("B", _i), ("C", _i), ("H", _i), ("W", _i),
                 ("P", _i), ("gh", _i), ("gw", _i), ("pad_top", _i), ("pad_left", _i)]
 
 
-class GemmArgs(C.Structure):
+class GemmArgs(Struct, c_name="mvp_gemm_args"):
     _fields_ = [("a_hi", _vp), ("a_lo", _vp), ("w_hi", _vp), ("w_lo", _vp), ("bias", _vp), ("residual", _vp),
                 ("out_f32", _vp), ("out_hi", _vp), ("out_lo", _vp), ("M", _i), ("N", _i), ("K", _i),
                 ("lda", _i), ("ldw", _i), ("ldr", _i), ("ldo", _i), ("ldob", _i), ("act", _i), ("precision", _i),
@@ -63,61 +73,61 @@ class GemmArgs(C.Structure):
                 ("out_f16_col0", _i)]
 
 
-class LayerNormArgs(C.Structure):
+class LayerNormArgs(Struct, c_name="mvp_layernorm_args"):
     _fields_ = [("x", _vp), ("gamma", _vp), ("beta", _vp), ("out_hi", _vp), ("out_lo", _vp), ("out_f32", _vp),
                 ("M", _i), ("C", _i), ("eps", _f), ("out_layout", _i), ("out_f16", _i)]
 
 
-class AttentionArgs(C.Structure):
+class AttentionArgs(Struct, c_name="mvp_attention_args"):
     _fields_ = [("qkv_hi", _vp), ("qkv_lo", _vp), ("out_hi", _vp), ("out_lo", _vp), ("B", _i), ("N", _i), ("H", _i),
                 ("ld_qkv", _i), ("ld_out", _i), ("scale", _f), ("precision", _i), ("out_layout", _i), ("v_format", _i), ("out_f16", _i)]
 
 
-class AttentionBiasArgs(C.Structure):  # mvp_attention_bias_args: attention with a dense per-head logit bias (added within ABI 8)
+class AttentionBiasArgs(Struct, c_name="mvp_attention_bias_args"):  # attention with a dense per-head logit bias (added within ABI 8)
     _fields_ = [("att", AttentionArgs), ("bias", _vp), ("bias_head_stride", _i64), ("ld_bias", _i)]
 
 
-class GatherRowsArgs(C.Structure):  # mvp_gather_rows_args: row gather of 16-bit pair buffers by an index table (added within ABI 8)
+class GatherRowsArgs(Struct, c_name="mvp_gather_rows_args"):  # row gather of 16-bit pair buffers by an index table (added within ABI 8)
     _fields_ = [("in_hi", _vp), ("in_lo", _vp), ("out_hi", _vp), ("out_lo", _vp), ("idx", _vp), ("rows", _i), ("rows_in", _i), ("cols", _i),
                 ("ld_in", _i), ("ld_out", _i)]
 
 
-class RelposTermsArgs(C.Structure):  # mvp_relpos_terms_args: SAM's decomposed relative-position terms (added within ABI 8)
+class RelposTermsArgs(Struct, c_name="mvp_relpos_terms_args"):  # SAM's decomposed relative-position terms (added within ABI 8)
     _fields_ = [("qkv", _vp), ("out_hi", _vp), ("out_lo", _vp), ("rel", _vp), ("rh", _vp), ("rw", _vp), ("rel_bh_stride", _i64),
                 ("M", _i), ("N", _i), ("H", _i), ("Qh", _i), ("Qw", _i), ("Kh", _i), ("Kw", _i), ("ld_in", _i), ("ld_out", _i), ("ld_rel", _i),
                 ("precision", _i), ("v_format", _i)]
 
 
-class AttentionRelposArgs(C.Structure):  # mvp_attention_relpos_args: attention with the decomposed bias (added within ABI 8)
+class AttentionRelposArgs(Struct, c_name="mvp_attention_relpos_args"):  # attention with the decomposed bias (added within ABI 8)
     _fields_ = [("att", AttentionArgs), ("rel", _vp), ("rel_bh_stride", _i64), ("ld_rel", _i), ("Kh", _i), ("Kw", _i)]
 
 
-class ClsRowsArgs(C.Structure):
+class ClsRowsArgs(Struct, c_name="mvp_cls_rows_args"):
     _fields_ = [("cls", _vp), ("pos0", _vp), ("x", _vp), ("B", _i), ("N", _i), ("C", _i)]
 
 
-class GemmScaledArgs(C.Structure):  # mvp_gemm_scaled_args: LayerScale in the GEMM epilogue (ABI 7 addition)
+class GemmScaledArgs(Struct, c_name="mvp_gemm_scaled_args"):  # LayerScale in the GEMM epilogue (ABI 7 addition)
     _fields_ = [("gemm", GemmArgs), ("col_scale", _vp)]
 
 
-class GemmRoute(C.Structure):  # mvp_gemm_route_t: the kernel mvp_gemm_bias_act_res runs (ABI 8)
+class GemmRoute(Struct, c_name="mvp_gemm_route_t"):  # the kernel mvp_gemm_bias_act_res runs (ABI 8)
     _fields_ = [("family", _i), ("bm", _i), ("bn", _i), ("bk", _i), ("split", _i), ("nstage", _i), ("nw", _i), ("wnw", _i)]
 
 
-class PatchGatherLdArgs(C.Structure):  # mvp_patch_gather_ld_args: padded patch rows (ABI 7 addition)
+class PatchGatherLdArgs(Struct, c_name="mvp_patch_gather_ld_args"):  # padded patch rows (ABI 7 addition)
     _fields_ = [("g", PatchGatherArgs), ("ldk", _i)]
 
 
-class PrefixRowsArgs(C.Structure):  # mvp_prefix_rows_args: CLS + register rows (ABI 7 addition)
+class PrefixRowsArgs(Struct, c_name="mvp_prefix_rows_args"):  # CLS + register rows (ABI 7 addition)
     _fields_ = [("cls", _vp), ("pos0", _vp), ("reg", _vp), ("x", _vp), ("B", _i), ("N", _i), ("C", _i), ("R", _i)]
 
 
-class Rope2dQkvArgs(C.Structure):  # mvp_rope2d_qkv_args: 2-D RoPE between the qkv GEMM and attention (added within ABI 8)
+class Rope2dQkvArgs(Struct, c_name="mvp_rope2d_qkv_args"):  # 2-D RoPE between the qkv GEMM and attention (added within ABI 8)
     _fields_ = [("qkv", _vp), ("out_hi", _vp), ("out_lo", _vp), ("cos_tab", _vp), ("sin_tab", _vp), ("M", _i), ("N", _i), ("H", _i),
                 ("n_prefix", _i), ("gh", _i), ("gw", _i), ("tab_rows", _i), ("ld_in", _i), ("ld_out", _i), ("precision", _i), ("v_format", _i)]
 
 
-class BnTokensArgs(C.Structure):
+class BnTokensArgs(Struct, c_name="mvp_bn_tokens_args"):
     _fields_ = [("x", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("stats", _vp),
                 ("nchw", _vp), ("tok_hi", _vp), ("tok_lo", _vp), ("ld_tok", _i), ("col_off", _i),
                 ("tokT_hi", _vp), ("tokT_lo", _vp), ("ldT", _i),
@@ -126,149 +136,149 @@ class BnTokensArgs(C.Structure):
                 ("defer_running", _i), ("groups", _i), ("stats_gstride", _i64), ("nchw_gstride", _i64), ("tok_gstride", _i64), ("cls_gstride", _i64)]
 
 
-class BnRunningUpdateArgs(C.Structure):
+class BnRunningUpdateArgs(Struct, c_name="mvp_bn_running_update_args"):
     _fields_ = [("stats", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp), ("C", _i), ("momentum", _f)]
 
 
-class PackNchwArgs(C.Structure):
+class PackNchwArgs(Struct, c_name="mvp_pack_nchw_args"):
     _fields_ = [("nchw", _vp), ("tok_hi", _vp), ("tok_lo", _vp), ("ld_tok", _i), ("col_off", _i),
                 ("tokT_hi", _vp), ("tokT_lo", _vp), ("ldT", _i), ("B", _i), ("C", _i), ("hw", _i)]
 
 
-class ResizeArgs(C.Structure):
+class ResizeArgs(Struct, c_name="mvp_resize_args"):
     _fields_ = [("src", _vp), ("dst", _vp), ("planes", _i), ("Hi", _i), ("Wi", _i), ("Ho", _i), ("Wo", _i),
                 ("mode", _i), ("align_corners", _i), ("channels_last", _i), ("C", _i), ("scale_h", _f), ("scale_w", _f)]
 
 
-class DepthPredictArgs(C.Structure):
+class DepthPredictArgs(Struct, c_name="mvp_depth_predict_args"):
     _fields_ = [("logits", _vp), ("depth", _vp), ("inv_sum", _vp), ("grad_depth", _vp), ("grad_logits", _vp),
                 ("P", _i64), ("K", _i), ("min_depth", _f), ("max_depth", _f), ("kind", _i)]
 
 
-class DepthLossArgs(C.Structure):
+class DepthLossArgs(Struct, c_name="mvp_depth_loss_args"):
     _fields_ = [("pred", _vp), ("target", _vp), ("loss", _vp), ("grad_pred", _vp), ("workspace", _vp),
                 ("workspace_bytes", _i64), ("B", _i), ("HW", _i64), ("w_sig", _f), ("w_grad", _f), ("max_depth", _f),
                 ("eps", _f), ("sigma", _f)]
 
 
-class AngularLossArgs(C.Structure):
+class AngularLossArgs(Struct, c_name="mvp_angular_loss_args"):
     _fields_ = [("pred", _vp), ("gt", _vp), ("mask", _vp), ("loss", _vp), ("grad_pred", _vp), ("workspace", _vp),
                 ("workspace_bytes", _i64), ("B", _i), ("Cp", _i), ("HW", _i64), ("eps", _f)]
 
 
-class ColsumArgs(C.Structure):
+class ColsumArgs(Struct, c_name="mvp_colsum_args"):
     _fields_ = [("x", _vp), ("out", _vp), ("M", _i), ("N", _i), ("ld", _i), ("accumulate", _i), ("workspace", _vp), ("workspace_bytes", _i64)]
 
 
-class AdamWArgs(C.Structure):
+class AdamWArgs(Struct, c_name="mvp_adamw_args"):
     _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("hyper", _vp), ("n", _i64),
                 ("beta1", _f), ("beta2", _f), ("eps", _f), ("weight_decay", _f), ("grad_scale", _f),
                 ("lr", _f), ("bias_c1", _f), ("bias_c2", _f)]
 
 
-class CorrArgmaxArgs(C.Structure):
+class CorrArgmaxArgs(Struct, c_name="mvp_corr_argmax_args"):
     _fields_ = [("src_feat", _vp), ("tgt_feat", _vp), ("kp_xy", _vp), ("out_xy", _vp), ("out_val", _vp),
                 ("workspace", _vp), ("workspace_bytes", _i64), ("C", _i), ("h", _i), ("w", _i), ("K", _i), ("heat_out", _vp)]
 
 
-class Argmax2dArgs(C.Structure):
+class Argmax2dArgs(Struct, c_name="mvp_argmax_2d_args"):
     _fields_ = [("x", _vp), ("out_xy", _vp), ("K", _i), ("h", _i), ("w", _i), ("max_value", _i)]
 
 
-class KnnRatioArgs(C.Structure):  # mvp_knn_ratio_args: top-2 cosine nearest neighbours + ratio test (added within ABI 8)
+class KnnRatioArgs(Struct, c_name="mvp_knn_ratio_args"):  # top-2 cosine nearest neighbours + ratio test (added within ABI 8)
     _fields_ = [("src_feat", _vp), ("tgt_feat", _vp), ("src_valid", _vp), ("tgt_valid", _vp), ("nn_idx", _vp), ("dist", _vp), ("weight", _vp),
                 ("n_valid", _vp), ("workspace", _vp), ("workspace_bytes", _i64), ("C", _i), ("N0", _i), ("N1", _i)]
 
 
-class PointcloudSampleArgs(C.Structure):  # mvp_pointcloud_sample_args: zero-padded bilinear sampling at projected points (added within ABI 8)
+class PointcloudSampleArgs(Struct, c_name="mvp_pointcloud_sample_args"):  # zero-padded bilinear sampling at projected points (added within ABI 8)
     _fields_ = [("feat", _vp), ("pc", _vp), ("K", _vp), ("out", _vp), ("valid", _vp), ("C", _i), ("fh", _i), ("fw", _i), ("N", _i),
                 ("H", _i), ("W", _i), ("ld_out", _i)]
 
 
-class TwoafcArgs(C.Structure):  # mvp_twoafc_args: pooled cosine scoring of 2AFC triplets + running confusion counts (added within ABI 8)
+class TwoafcArgs(Struct, c_name="mvp_twoafc_args"):  # pooled cosine scoring of 2AFC triplets + running confusion counts (added within ABI 8)
     _fields_ = [("ref", _vp), ("left", _vp), ("right", _vp), ("label", _vp), ("sim", _vp), ("pred", _vp), ("counts", _vp),
                 ("workspace", _vp), ("workspace_bytes", _i64), ("ld", _i64), ("B", _i), ("C", _i), ("HW", _i), ("accumulate", _i)]
 
 
-class BnActArgs(C.Structure):  # mvp_bn_act_args: BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
+class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
                 ("B", _i), ("HW", _i64), ("C", _i), ("ld", _i), ("n", _i64), ("eps", _f), ("momentum", _f), ("act", _i), ("training", _i), ("accumulate", _i)]
 
 
-class BceLossArgs(C.Structure):  # mvp_bce_loss_args: nn.BCELoss (mean) and its gradient (added within ABI 8)
+class BceLossArgs(Struct, c_name="mvp_bce_loss_args"):  # nn.BCELoss (mean) and its gradient (added within ABI 8)
     _fields_ = [("pred", _vp), ("target", _vp), ("loss", _vp), ("grad_pred", _vp), ("workspace", _vp), ("workspace_bytes", _i64), ("N", _i64)]
 
 
-class BinaryCountsArgs(C.Structure):  # mvp_binary_counts_args: TP / FP / FN / TN of a thresholded prediction (added within ABI 8)
+class BinaryCountsArgs(Struct, c_name="mvp_binary_counts_args"):  # TP / FP / FN / TN of a thresholded prediction (added within ABI 8)
     _fields_ = [("pred", _vp), ("gt", _vp), ("counts", _vp), ("G", _i), ("n", _i64), ("threshold", _f)]
 
 
-class ScaleShiftArgs(C.Structure):
+class ScaleShiftArgs(Struct, c_name="mvp_scale_shift_args"):
     _fields_ = [("x", _vp), ("scale_shift", _vp), ("grad_out", _vp), ("out", _vp), ("B", _i), ("HW", _i64), ("lo", _f), ("hi", _f),
                 ("clamp", _i), ("backward", _i)]
 
 
-class MetricsBreakdownArgs(C.Structure):
+class MetricsBreakdownArgs(Struct, c_name="mvp_metrics_breakdown_args"):
     _fields_ = [("pred", _vp), ("gt", _vp), ("seg", _vp), ("scale_shift", _vp), ("level_sums", _vp), ("seg_sums", _vp),
                 ("workspace", _vp), ("workspace_bytes", _i64), ("B", _i), ("H", _i), ("W", _i), ("Cp", _i), ("num_levels", _i), ("num_ids", _i),
                 ("t1", _f), ("t2", _f), ("t3", _f)]
 
 
-class ConvWeightPackArgs(C.Structure):
+class ConvWeightPackArgs(Struct, c_name="mvp_conv_weight_pack_args"):
     _fields_ = [("w", _vp), ("out_hi", _vp), ("out_lo", _vp), ("Cout", _i), ("Cin", _i), ("kh", _i), ("kw", _i), ("mode", _i)]
 
 
-class UpsampleClArgs(C.Structure):
+class UpsampleClArgs(Struct, c_name="mvp_upsample_cl_args"):
     _fields_ = [("src", _vp), ("dst_f32", _vp), ("dst_hi", _vp), ("dst_lo", _vp), ("B", _i), ("H", _i), ("W", _i), ("C", _i),
                 ("f", _i), ("backward", _i)]
 
 
-class UpconvBoxsumArgs(C.Structure):
+class UpconvBoxsumArgs(Struct, c_name="mvp_upconv_boxsum_args"):
     _fields_ = [("g", _vp), ("out_hi", _vp), ("out_lo", _vp), ("B", _i), ("H", _i), ("W", _i), ("C", _i), ("f", _i)]
 
 
-class UpconvGatherArgs(C.Structure):
+class UpconvGatherArgs(Struct, c_name="mvp_upconv_gather_args"):
     _fields_ = [("t", _vp), ("bias", _vp), ("out_f32", _vp), ("out_hi", _vp), ("out_lo", _vp), ("out_mask", _vp),
                 ("B", _i), ("H", _i), ("W", _i), ("C", _i), ("f", _i), ("act", _i)]
 
 
-class DepthMetricsArgs(C.Structure):
+class DepthMetricsArgs(Struct, c_name="mvp_depth_metrics_args"):
     _fields_ = [("pred", _vp), ("gt", _vp), ("out", _vp), ("scale_shift", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
                 ("B", _i), ("HW", _i64), ("scale_invariant", _i)]
 
 
-class SnormMetricsArgs(C.Structure):
+class SnormMetricsArgs(Struct, c_name="mvp_snorm_metrics_args"):
     _fields_ = [("pred", _vp), ("gt", _vp), ("out", _vp), ("workspace", _vp), ("workspace_bytes", _i64), ("B", _i), ("Cp", _i),
                 ("HW", _i64), ("t1", _f), ("t2", _f), ("t3", _f)]
 
 
-class LinearBinsArgs(C.Structure):
+class LinearBinsArgs(Struct, c_name="mvp_linear_bins_args"):
     _fields_ = [("l0", _vp), ("depth", _vp), ("inv_sum", _vp), ("gate", _vp), ("grad_depth", _vp), ("grad_l0", _vp),
                 ("B", _i), ("h", _i), ("w", _i), ("K", _i), ("f", _i), ("min_depth", _f), ("max_depth", _f)]
 
 
-class Im2colArgs(C.Structure):
+class Im2colArgs(Struct, c_name="mvp_im2col_args"):
     _fields_ = [("src", _vp), ("out_hi", _vp), ("out_lo", _vp), ("B", _i), ("C", _i), ("H", _i), ("W", _i), ("Ho", _i), ("Wo", _i),
                 ("kh", _i), ("kw", _i), ("stride", _i), ("pad", _i), ("ldk", _i)]
 
 
-class MaxpoolClArgs(C.Structure):
+class MaxpoolClArgs(Struct, c_name="mvp_maxpool_cl_args"):
     _fields_ = [("src", _vp), ("dst_f32", _vp), ("dst_hi", _vp), ("dst_lo", _vp), ("B", _i), ("H", _i), ("W", _i), ("C", _i),
                 ("Ho", _i), ("Wo", _i), ("k", _i), ("stride", _i), ("pad", _i)]
 
 
-class StemArgs(C.Structure):
+class StemArgs(Struct, c_name="mvp_stem_args"):
     _fields_ = [("images", _vp), ("w_hi", _vp), ("w_lo", _vp), ("bias", _vp), ("out_f32", _vp), ("out_hi", _vp), ("out_lo", _vp),
                 ("B", _i), ("H", _i), ("W", _i), ("precision", _i)]
 
 
-class MaskSplitArgs(C.Structure):
+class MaskSplitArgs(Struct, c_name="mvp_mask_split_args"):
     _fields_ = [("src", _vp), ("mask", _vp), ("dst_f32", _vp), ("dst_hi", _vp), ("dst_lo", _vp), ("M", _i64), ("N", _i),
                 ("lds", _i), ("ldm", _i), ("ldo", _i), ("relu_mask_out", _vp)]
 
 
-class GemmTnArgs(C.Structure):
+class GemmTnArgs(Struct, c_name="mvp_gemm_tn_args"):
     _fields_ = [("g_hi", _vp), ("g_lo", _vp), ("x_hi", _vp), ("x_lo", _vp), ("partial", _vp), ("dw", _vp), ("zero_page", _vp),
                 ("M", _i64), ("Cout", _i), ("Cin", _i), ("ldg", _i), ("ldx", _i), ("H", _i), ("W", _i), ("Ho", _i), ("Wo", _i),
                 ("kh", _i), ("kw", _i), ("stride", _i), ("pad", _i), ("up", _i), ("splits", _i), ("accumulate", _i), ("precision", _i)]
@@ -344,15 +354,24 @@ SYMBOLS = {
     "mvp_twoafc_workspace_bytes": None,
 }
 
-# the ctypes mirror of every argument struct the additions of ABI 7 brought (tests compare them with mvp_sizeof)
-NEW_STRUCTS_ABI7 = {"mvp_gemm_scaled_args": GemmScaledArgs, "mvp_patch_gather_ld_args": PatchGatherLdArgs, "mvp_prefix_rows_args": PrefixRowsArgs}
-
-NEW_STRUCTS_ABI8 = {"mvp_gemm_route_t": GemmRoute, "mvp_rope2d_qkv_args": Rope2dQkvArgs, "mvp_attention_bias_args": AttentionBiasArgs,
-                    "mvp_gather_rows_args": GatherRowsArgs, "mvp_relpos_terms_args": RelposTermsArgs,
-                    "mvp_attention_relpos_args": AttentionRelposArgs, "mvp_knn_ratio_args": KnnRatioArgs,
-                    "mvp_bn_act_args": BnActArgs, "mvp_bce_loss_args": BceLossArgs,
-                    "mvp_binary_counts_args": BinaryCountsArgs, "mvp_pointcloud_sample_args": PointcloudSampleArgs,
-                    "mvp_twoafc_args": TwoafcArgs}  # the same for the additions of / within ABI 8
+# the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)
+SIGNATURES = {
+    "mvp_get_info": (_i, [C.POINTER(Info)]),
+    "mvp_strerror": (C.c_char_p, [_i]),
+    "mvp_sizeof": (_i, [C.c_char_p]),
+    "mvp_gemm_splitk_workspace_bytes": (_i64, [_i, _i, _i]),
+    "mvp_gemm_route": (_i, [C.POINTER(GemmArgs), C.POINTER(GemmRoute)]),
+    "mvp_bn_tokens_workspace_bytes": (_i64, [_i, _i]),
+    "mvp_bn_running_update_n": (_i, [C.POINTER(BnRunningUpdateArgs), _i, _vp]),
+    "mvp_depth_loss_workspace_bytes": (_i64, [_i, _i64]),
+    "mvp_colsum_workspace_bytes": (_i64, [_i, _i]),
+    "mvp_corr_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "mvp_metrics_breakdown_workspace_bytes": (_i64, [_i, _i, _i]),
+    "mvp_metrics_workspace_bytes": (_i64, [_i]),
+    "mvp_gemm_tn_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "mvp_knn_workspace_bytes": (_i64, [_i, _i, _i]),
+    "mvp_twoafc_workspace_bytes": (_i64, [_i, _i, _i]),
+}
 
 _lib: Optional[C.CDLL] = None
 
@@ -368,41 +387,10 @@ def load() -> C.CDLL:
             "(or `make -C midvision-probe_amd/csrc`). There is no CPU fallback for the product path."
         )
     lib = C.CDLL(LIB_PATH)
+    assert set(SIGNATURES) == {name for name, st in SYMBOLS.items() if st is None}
     for name, st in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-        if st is not None:
-            fn.argtypes = [C.POINTER(st), _vp]
-            fn.restype = _i
-    lib.mvp_bn_running_update_n.argtypes = [C.POINTER(BnRunningUpdateArgs), _i, _vp]
-    lib.mvp_bn_running_update_n.restype = _i
-    lib.mvp_get_info.argtypes = [C.POINTER(Info)]
-    lib.mvp_get_info.restype = _i
-    lib.mvp_strerror.argtypes = [_i]
-    lib.mvp_strerror.restype = C.c_char_p
-    lib.mvp_corr_workspace_bytes.argtypes = [_i, _i, _i, _i]
-    lib.mvp_corr_workspace_bytes.restype = _i64
-    lib.mvp_knn_workspace_bytes.argtypes = [_i, _i, _i]
-    lib.mvp_knn_workspace_bytes.restype = _i64
-    lib.mvp_twoafc_workspace_bytes.argtypes = [_i, _i, _i]
-    lib.mvp_twoafc_workspace_bytes.restype = _i64
-    lib.mvp_sizeof.argtypes = [C.c_char_p]
-    lib.mvp_sizeof.restype = _i
-    lib.mvp_bn_tokens_workspace_bytes.argtypes = [_i, _i]
-    lib.mvp_bn_tokens_workspace_bytes.restype = _i64
-    lib.mvp_colsum_workspace_bytes.argtypes = [_i, _i]
-    lib.mvp_colsum_workspace_bytes.restype = _i64
-    lib.mvp_metrics_breakdown_workspace_bytes.argtypes = [_i, _i, _i]
-    lib.mvp_metrics_breakdown_workspace_bytes.restype = _i64
-    lib.mvp_metrics_workspace_bytes.argtypes = [_i]
-    lib.mvp_metrics_workspace_bytes.restype = _i64
-    lib.mvp_gemm_route.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmRoute)]
-    lib.mvp_gemm_route.restype = _i
-    lib.mvp_gemm_splitk_workspace_bytes.argtypes = [_i, _i, _i]
-    lib.mvp_gemm_splitk_workspace_bytes.restype = _i64
-    lib.mvp_gemm_tn_workspace_bytes.argtypes = [_i, _i, _i, _i, _i]
-    lib.mvp_gemm_tn_workspace_bytes.restype = _i64
-    lib.mvp_depth_loss_workspace_bytes.argtypes = [_i, _i64]
-    lib.mvp_depth_loss_workspace_bytes.restype = _i64
+        fn.restype, fn.argtypes = (_i, [C.POINTER(st), _vp]) if st is not None else SIGNATURES[name]
     _lib = lib
     return lib
 

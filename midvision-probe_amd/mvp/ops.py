@@ -87,6 +87,13 @@ def _chk(t: torch.Tensor, dtype, name: str):
         raise lib.MvpError(f"{name}: expected contiguous {dtype} device tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
 
 
+def _v_format(who: str, v_f16: bool, qk_f16: bool) -> int:
+    """mvp_attention_args.v_format of the (v_f16, qk_f16) a wrapper was given."""
+    if qk_f16 and not v_f16:
+        raise lib.MvpError(f"{who}: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
+    return (lib.ATT_V_F16_QK_F16 if qk_f16 else lib.ATT_V_F16) if v_f16 else lib.ATT_V_BF16_PAIR
+
+
 def empty_pair(shape, precision: int, device) -> Pair:
     hi = torch.empty(shape, dtype=torch.bfloat16, device=device)
     lo = torch.empty(shape, dtype=torch.bfloat16, device=device) if precision == PREC_BF16X3 else None
@@ -290,14 +297,13 @@ def attention(qkv: Pair, out: Pair, B: int, N: int, H: int, scale: float, precis
     anything).  None: mvp_attention_fwd, exactly as before.
     ``rel`` with ``rel_grid`` = (Kh, Kw), Kh * Kw == N: fp32 [B * H, N, ld_rel] as ``relpos_terms`` writes it; softmax(Q K^T * scale +
     rel[bh][q][k // Kw] + rel[bh][q][Kh + k % Kw]) (mvp_attention_relpos_fwd: SAM's decomposed relative-position bias, never densified)."""
-    if qk_f16 and not v_f16:
-        raise lib.MvpError("attention: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
+    v_format = _v_format("attention", v_f16, qk_f16)
     ilv = isinstance(out, IlvPair)
     if ilv:
         out, ld_out = (out.t, None), (ld_out if ld_out is not None else 2 * H * 64)
     a = lib.AttentionArgs(lib.ptr(qkv[0]), lib.ptr(qkv[1]), lib.ptr(out[0]), lib.ptr(out[1]), B, N, H,
                           ld_qkv if ld_qkv is not None else 3 * H * 64, ld_out if ld_out is not None else H * 64, scale, precision,
-                          lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE, (2 if qk_f16 else 1) if v_f16 else 0, 1 if out_f16 else 0)
+                          lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE, v_format, 1 if out_f16 else 0)
     if rel is not None:
         if bias is not None:
             raise lib.MvpError("attention: a dense bias and decomposed relative-position terms exclude each other")
@@ -322,15 +328,14 @@ def rope2d_qkv(qkv_f32: torch.Tensor, out: Pair, cos_tab: torch.Tensor, sin_tab:
     ``out`` that ``attention`` reads, Q and K rotated by each token's (y, x) grid position, V passed through, every third in the form
     ``gemm(..., f16_col0=...)`` writes for the same ``v_f16`` / ``qk_f16`` (see ``attention``).  ``cos_tab`` / ``sin_tab``: fp32
     [rows >= max(gh, gw), 32], row = grid coordinate."""
-    if qk_f16 and not v_f16:
-        raise lib.MvpError("rope2d_qkv: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
+    v_format = _v_format("rope2d_qkv", v_f16, qk_f16)
     _chk(cos_tab, torch.float32, "rope2d_qkv.cos_tab")
     _chk(sin_tab, torch.float32, "rope2d_qkv.sin_tab")
     if qkv_f32.dtype != torch.float32 or cos_tab.dim() != 2 or cos_tab.shape[1] != 32 or sin_tab.shape != cos_tab.shape:
         raise lib.MvpError("rope2d_qkv: fp32 projection and fp32 [rows, 32] cos / sin tables of one shape expected")
     a = lib.Rope2dQkvArgs(lib.ptr(qkv_f32), lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(cos_tab), lib.ptr(sin_tab), M, N, H, n_prefix, gh, gw,
                           int(cos_tab.shape[0]), ld_in if ld_in is not None else 3 * H * 64, ld_out if ld_out is not None else 3 * H * 64,
-                          precision, (2 if qk_f16 else 1) if v_f16 else 0)
+                          precision, v_format)
     # algorithmic HBM bytes: the fp32 projection read once, the 16-bit pair (or single bf16) written once
     nb = M * 3 * H * 64 * (4 + (4 if out[1] is not None else 2))
     _traced("hbm", "rope2d_qkv_kernel", 0, float(nb), lambda: lib.call("mvp_rope2d_qkv", a))
@@ -342,8 +347,7 @@ def relpos_terms(qkv_f32: torch.Tensor, out: Pair, rel: torch.Tensor, rh: torch.
     ``rel`` fp32 [M // N * H, N, ld_rel], rel[bh][q][ky] = q . rh[yq][ky], rel[bh][q][Kh + kx] = q . rw[xq][kx] on the UNSCALED q, and the
     pair ``out`` that ``attention`` reads, every third in the form ``gemm(..., f16_col0=...)`` writes for the same ``v_f16`` / ``qk_f16``.
     ``rh`` fp32 [Qh, Kh, 64], ``rw`` fp32 [Qw, Kw, 64], Qh * Qw == N."""
-    if qk_f16 and not v_f16:
-        raise lib.MvpError("relpos_terms: qk_f16 needs v_f16 (mvp_attention_args.v_format = MVP_ATT_V_F16_QK_F16)")
+    v_format = _v_format("relpos_terms", v_f16, qk_f16)
     _chk(rh, torch.float32, "relpos_terms.rh")
     _chk(rw, torch.float32, "relpos_terms.rw")
     if qkv_f32.dtype != torch.float32 or rh.dim() != 3 or rw.dim() != 3 or rh.shape[2] != 64 or rw.shape[2] != 64:
@@ -353,7 +357,7 @@ def relpos_terms(qkv_f32: torch.Tensor, out: Pair, rel: torch.Tensor, rh: torch.
     a = lib.RelposTermsArgs(lib.ptr(qkv_f32), lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(rel), lib.ptr(rh), lib.ptr(rw), rel.stride(0), M, N, H,
                             int(rh.shape[0]), int(rw.shape[0]), int(rh.shape[1]), int(rw.shape[1]),
                             ld_in if ld_in is not None else 3 * H * 64, ld_out if ld_out is not None else 3 * H * 64, rel.stride(1),
-                            precision, (2 if qk_f16 else 1) if v_f16 else 0)
+                            precision, v_format)
     nb = M * 3 * H * 64 * (4 + (4 if out[1] is not None else 2)) + M * H * (rh.shape[1] + rw.shape[1]) * 4
     _traced("hbm", "relpos_terms_kernel", 0, float(nb), lambda: lib.call("mvp_relpos_terms", a))
 

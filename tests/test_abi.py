@@ -1,12 +1,16 @@
 """CPU checks of the drop-in boundary: the C-ABI library loads and exports every symbol that
-include/mvp_hip.h declares; argument validation returns error codes (no compute, no GPU)."""
+include/mvp_hip.h declares; mvp/lib.py's structs, signatures and constants are the header's, field by field
+(tests/abi_header.py reads it); argument validation returns error codes (no compute, no GPU)."""
 import ctypes
+import functools
 import os
 import re
 
 import pytest
 
+import abi_header
 from conftest import REPO
+from mvp import lib
 
 
 def _declared():
@@ -19,7 +23,7 @@ def test_header_symbols_are_exported_and_bound():
 
     declared = _declared()
     assert len(declared) >= 20
-    assert set(declared) == set(lib.SYMBOLS), set(declared) ^ set(lib.SYMBOLS)
+    assert set(declared) == set(lib.SYMBOLS) == set(_header()[1]), set(declared) ^ set(lib.SYMBOLS)
     so = lib.load()
     for name in declared:
         assert hasattr(so, name), name
@@ -59,32 +63,60 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
         lib.load()
 
 
-def test_ctypes_structs_match_the_compiled_header():
-    """Every ctypes mirror in mvp/lib.py has the size the C compiler gave the struct of include/mvp_hip.h
-    (mvp_sizeof): catches field-order / padding drift between the header and the binding."""
-    from mvp import lib
+@functools.lru_cache(None)
+def _header():
+    """(structs, prototypes, defines) of include/mvp_hip.h, as ctypes types (tests/abi_header.py)."""
+    return abi_header.parse(lib.STRUCTS)
 
+
+def test_every_header_struct_has_one_mirror():
+    assert set(_header()[0]) == set(lib.STRUCTS), set(_header()[0]) ^ set(lib.STRUCTS)
+
+
+@pytest.mark.parametrize("cname", sorted(lib.STRUCTS))
+def test_mirror_fields_match_the_header(cname):
+    """Name, order and ctypes type of every field: two neighbours of one size swapped in a mirror, or a float bound as an int, keep
+    sizeof and hand the kernel wrong arguments (mvp/ops.py builds most structs positionally)."""
+    assert lib.STRUCTS[cname]._fields_ == _header()[0][cname], cname
+
+
+def test_ctypes_structs_match_the_compiled_header():
+    """Every ctypes mirror in mvp/lib.py has the size the C compiler gave the struct of include/mvp_hip.h (mvp_sizeof); an entry
+    missing from info.hip's MVP_SZ list answers -1."""
     so = lib.load()
-    names = {
-        "mvp_info_t": lib.Info, "mvp_split_bf16_args": lib.SplitArgs, "mvp_patch_gather_args": lib.PatchGatherArgs,
-        "mvp_gemm_args": lib.GemmArgs, "mvp_layernorm_args": lib.LayerNormArgs, "mvp_attention_args": lib.AttentionArgs,
-        "mvp_cls_rows_args": lib.ClsRowsArgs, "mvp_bn_tokens_args": lib.BnTokensArgs, "mvp_pack_nchw_args": lib.PackNchwArgs,
-        "mvp_resize_args": lib.ResizeArgs, "mvp_depth_predict_args": lib.DepthPredictArgs, "mvp_depth_loss_args": lib.DepthLossArgs,
-        "mvp_angular_loss_args": lib.AngularLossArgs, "mvp_colsum_args": lib.ColsumArgs, "mvp_adamw_args": lib.AdamWArgs,
-        "mvp_corr_argmax_args": lib.CorrArgmaxArgs, "mvp_conv_weight_pack_args": lib.ConvWeightPackArgs,
-        "mvp_upsample_cl_args": lib.UpsampleClArgs, "mvp_gemm_tn_args": lib.GemmTnArgs, "mvp_depth_metrics_args": lib.DepthMetricsArgs,
-        "mvp_snorm_metrics_args": lib.SnormMetricsArgs, "mvp_linear_bins_args": lib.LinearBinsArgs, "mvp_im2col_args": lib.Im2colArgs,
-        "mvp_maxpool_cl_args": lib.MaxpoolClArgs, "mvp_mask_split_args": lib.MaskSplitArgs,
-        "mvp_metrics_breakdown_args": lib.MetricsBreakdownArgs, "mvp_argmax_2d_args": lib.Argmax2dArgs, "mvp_scale_shift_args": lib.ScaleShiftArgs, "mvp_stem_args": lib.StemArgs,
-        "mvp_bn_running_update_args": lib.BnRunningUpdateArgs, "mvp_upconv_boxsum_args": lib.UpconvBoxsumArgs, "mvp_upconv_gather_args": lib.UpconvGatherArgs,
-    }
-    import re
-    header = open(os.path.join(os.path.dirname(__file__), "..", "include", "mvp_hip.h")).read()
-    declared = set(re.findall(r"^\} (mvp_\w+);", header, flags=re.M))
-    assert declared == set(names), declared ^ set(names)
-    for cname, cls in names.items():
-        assert so.mvp_sizeof(cname.encode()) == ctypes.sizeof(cls), (cname, so.mvp_sizeof(cname.encode()), ctypes.sizeof(cls))
+    for cname in _header()[0]:
+        assert so.mvp_sizeof(cname.encode()) == ctypes.sizeof(lib.STRUCTS[cname]), (cname, so.mvp_sizeof(cname.encode()))
     assert so.mvp_sizeof(b"nope") == -1
+
+
+@pytest.mark.parametrize("name", sorted(lib.SYMBOLS))
+def test_bound_signature_matches_the_header(name):
+    """restype and argtypes of every loaded function are the header's prototype; for `int f(const T*, void* stream)` that is
+    SYMBOLS[f] is STRUCTS[T]."""
+    fn = getattr(lib.load(), name)
+    assert (fn.restype, list(fn.argtypes)) == _header()[1][name], name
+
+
+# the constants mvp/lib.py copies from the header: lib.<X> is MVP_<X>, the GEMM route families excepted
+CONSTANTS = ("PREC_BF16 PREC_BF16X3 PREC_F16X2 ACT_NONE ACT_GELU ACT_RELU ACT_QUICK_GELU ACT_GELU_TANH RESIZE_NEAREST RESIZE_BILINEAR "
+             "RESIZE_BICUBIC PAIR_SEPARATE PAIR_A_ILV32 PAIR_W_ILV32 BN_ACT_NONE BN_ACT_SIGMOID BN_ACT_TANH BN_ACT_WORKSPACE_BYTES "
+             "BCE_WORKSPACE_BYTES BN_RUNNING_MAX TILES_SHARED TILES_NO_PP TILES_NO_UNI ROUTE_PP ROUTE_TILE ROUTE_SPLITK ROUTE_CONV "
+             "ATT_V_BF16_PAIR ATT_V_F16 ATT_V_F16_QK_F16").split()
+
+
+def _header_name(x):
+    return "MVP_GEMM_" + x if x.startswith("ROUTE_") else "MVP_" + x
+
+
+def test_the_expected_constants_are_the_ones_lib_defines():
+    defines = _header()[2]
+    found = {x for x, v in vars(lib).items() if x.isupper() and isinstance(v, int) and _header_name(x) in defines}
+    assert len(CONSTANTS) == 30 and found == set(CONSTANTS), found ^ set(CONSTANTS)
+
+
+@pytest.mark.parametrize("x", CONSTANTS)
+def test_constant_equals_the_header_define(x):
+    assert getattr(lib, x) == _header()[2][_header_name(x)], x
 
 
 def test_integration_md_binding_matches_the_header():

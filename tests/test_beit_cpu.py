@@ -234,7 +234,7 @@ def test_attention_bias_abi():
     assert so.mvp_sizeof(b"mvp_attention_bias_args") == C.sizeof(lib.AttentionBiasArgs) == C.sizeof(lib.AttentionArgs) + 24
     assert so.mvp_sizeof(b"mvp_attention_args") == C.sizeof(lib.AttentionArgs)
     assert lib.info().abi_version == 8
-    assert lib.NEW_STRUCTS_ABI8["mvp_attention_bias_args"] is lib.AttentionBiasArgs
+    assert lib.STRUCTS["mvp_attention_bias_args"] is lib.AttentionBiasArgs
     header = open(os.path.join(REPO, "include", "mvp_hip.h")).read()
     assert "Added within 8: mvp_attention_bias_fwd" in header and "struct mvp_attention_bias_args {" in header
     assert "#define MVP_ABI_VERSION 8" in header

@@ -144,7 +144,7 @@ def test_knn_abi_struct_workspace_and_einval():
 
     so = lib.load()
     assert so.mvp_sizeof(b"mvp_knn_ratio_args") == ctypes.sizeof(lib.KnnRatioArgs) == 96
-    assert lib.NEW_STRUCTS_ABI8["mvp_knn_ratio_args"] is lib.KnnRatioArgs and lib.SYMBOLS["mvp_knn_ratio"] is lib.KnnRatioArgs
+    assert lib.STRUCTS["mvp_knn_ratio_args"] is lib.KnnRatioArgs and lib.SYMBOLS["mvp_knn_ratio"] is lib.KnnRatioArgs
     assert lib.info().abi_version == 8
     assert so.mvp_knn_workspace_bytes(64, 300, 333) == _ws_bytes(64, 300, 333) == 352896
     assert so.mvp_knn_workspace_bytes(768, 16384, 16384) == _ws_bytes(768, 16384, 16384) == 203423744

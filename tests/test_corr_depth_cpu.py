@@ -120,7 +120,7 @@ def test_pointcloud_sample_abi_struct_and_einval():
 
     so = lib.load()
     assert so.mvp_sizeof(b"mvp_pointcloud_sample_args") == ctypes.sizeof(lib.PointcloudSampleArgs) == 72
-    assert lib.NEW_STRUCTS_ABI8["mvp_pointcloud_sample_args"] is lib.PointcloudSampleArgs
+    assert lib.STRUCTS["mvp_pointcloud_sample_args"] is lib.PointcloudSampleArgs
     assert lib.SYMBOLS["mvp_pointcloud_sample"] is lib.PointcloudSampleArgs
     assert lib.info().abi_version == 8
     ok = dict(feat=256, pc=256, K=256, out=256, valid=256, C=4, fh=3, fw=5, N=8, H=6, W=10, ld_out=8)

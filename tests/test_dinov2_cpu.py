@@ -124,8 +124,8 @@ def test_new_exports_declared_bound_and_sized():
     for name, st in (("mvp_gemm_scaled", lib.GemmScaledArgs), ("mvp_patch_gather_ld", lib.PatchGatherLdArgs), ("mvp_prefix_rows", lib.PrefixRowsArgs)):
         assert re.search(rf"^int {name}\(", hdr, flags=re.M), name
         assert lib.SYMBOLS[name] is st and hasattr(so, name)
-    for cname, cls in lib.NEW_STRUCTS_ABI7.items():
-        assert so.mvp_sizeof(cname.encode()) == __import__("ctypes").sizeof(cls), cname
+    for cname in ("mvp_gemm_scaled_args", "mvp_patch_gather_ld_args", "mvp_prefix_rows_args"):
+        assert so.mvp_sizeof(cname.encode()) == __import__("ctypes").sizeof(lib.STRUCTS[cname]), cname
     assert so.mvp_sizeof(b"mvp_gemm_scaled_args") == so.mvp_sizeof(b"mvp_gemm_args") + 8
     integ = open(os.path.join(REPO, "INTEGRATION.md")).read()
     for name in ("mvp_gemm_scaled", "mvp_patch_gather_ld", "mvp_prefix_rows"):

@@ -297,7 +297,7 @@ def test_new_exports_reject_bad_arguments():
 
     so = lib.load()
     for cname, st in (("mvp_bn_act_args", lib.BnActArgs), ("mvp_bce_loss_args", lib.BceLossArgs), ("mvp_binary_counts_args", lib.BinaryCountsArgs)):
-        assert so.mvp_sizeof(cname.encode()) == ctypes.sizeof(st) and lib.NEW_STRUCTS_ABI8[cname] is st
+        assert so.mvp_sizeof(cname.encode()) == ctypes.sizeof(st) and lib.STRUCTS[cname] is st
     ok = dict(x=16, y=16, gamma=16, beta=16, running_mean=16, running_var=16, stats=16, workspace=16, workspace_bytes=lib.BN_ACT_WORKSPACE_BYTES,
               B=2, HW=8, C=2, ld=4, n=16, eps=1e-5, momentum=0.1, act=lib.BN_ACT_SIGMOID, training=1)
     for bad in (dict(x=None), dict(y=None), dict(C=0), dict(C=9), dict(ld=1), dict(B=0), dict(HW=0), dict(act=3), dict(gamma=None), dict(stats=None),

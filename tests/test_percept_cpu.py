@@ -21,7 +21,7 @@ def test_symbols_are_exported_declared_and_bound():
     for name in ("mvp_twoafc_score", "mvp_twoafc_workspace_bytes"):
         assert re.search(r"^\s*(?:int|int64_t)\s+" + name + r"\s*\(", header, flags=re.M), name
         assert name in lib.SYMBOLS and hasattr(so, name)
-    assert lib.SYMBOLS["mvp_twoafc_score"] is lib.TwoafcArgs and lib.NEW_STRUCTS_ABI8["mvp_twoafc_args"] is lib.TwoafcArgs
+    assert lib.SYMBOLS["mvp_twoafc_score"] is lib.TwoafcArgs and lib.STRUCTS["mvp_twoafc_args"] is lib.TwoafcArgs
     assert "struct mvp_twoafc_args {" in header and so.mvp_sizeof(b"mvp_twoafc_args") == ctypes.sizeof(lib.TwoafcArgs)
     assert lib.info().abi_version == 8
     from mvp import ops, percept

@@ -193,7 +193,7 @@ def test_sam_exports_abi():
     for sym, st, cname in (("mvp_gather_rows", lib.GatherRowsArgs, b"mvp_gather_rows_args"), ("mvp_relpos_terms", lib.RelposTermsArgs, b"mvp_relpos_terms_args"),
                            ("mvp_attention_relpos_fwd", lib.AttentionRelposArgs, b"mvp_attention_relpos_args")):
         assert hasattr(so, sym) and lib.SYMBOLS[sym] is st
-        assert so.mvp_sizeof(cname) == C.sizeof(st) and lib.NEW_STRUCTS_ABI8[cname.decode()] is st
+        assert so.mvp_sizeof(cname) == C.sizeof(st) and lib.STRUCTS[cname.decode()] is st
     assert C.sizeof(lib.AttentionRelposArgs) == C.sizeof(lib.AttentionArgs) + 32  # pointer, int64, three ints, padded to 8
     assert so.mvp_sizeof(b"mvp_attention_args") == C.sizeof(lib.AttentionArgs) and so.mvp_sizeof(b"mvp_attention_bias_args") == C.sizeof(lib.AttentionBiasArgs)
     assert lib.info().abi_version == 8
