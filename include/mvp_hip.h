@@ -90,6 +90,9 @@ typedef struct {
                                 Added within 8: mvp_twoafc_score and mvp_twoafc_workspace_bytes (pooled cosine scoring of 2AFC triplets with the
                                 running confusion counts, the perceptual-similarity evaluation); new exports with their own tagged argument struct,
                                 no existing struct changed.
+                                Added within 8: mvp_ncut_affinity, mvp_ncut_threshold, mvp_ncut_fiedler, mvp_ncut_partition and
+                                mvp_ncut_workspace_bytes (MaskCut: thresholded patch affinity, LDS-resident normalised-cut solver, partition);
+                                new exports with their own tagged argument structs, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -824,6 +827,83 @@ struct mvp_twoafc_args {
  * mvp_twoafc_score rejects. */
 int64_t mvp_twoafc_workspace_bytes(int B, int C, int HW);
 int mvp_twoafc_score(const mvp_twoafc_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; new exports with their own tagged argument structs, no existing struct changed.)
+ * MaskCut: normalised cuts on the patch affinity of a backbone's last-layer keys (evals/models/maskcut_processor.py of the
+ * reference: get_affinity_matrix, second_smallest_eigenvector, get_salient_areas, check_num_fg_corners, detect_box and the loop of
+ * maskcut_forward), one pass = four launches batched over Bimg images, none of which talks to the host.  N = h * w cells of the patch
+ * grid, N <= 1024, C <= 4096, Bimg <= 65535.  Every launch takes `active` (optional [Bimg] bytes; NULL = all): the workgroups of an
+ * image whose byte is 0 return at once and none of that image's outputs is written.  No floating-point atomics; two calls give the
+ * same bits.  eps = 1e-5 is the reference's off-weight.
+ *
+ * mvp_ncut_affinity: feats [Bimg, C, ldf] fp32 channel-major (image b at element b * C * ldf; columns N..ldf-1 never read), painted
+ * optional [Bimg, N] bytes.  f_n = column n divided by max(|column n|, 1e-12) (F.normalize; norm in fp64), or 0 where painted[n] != 0;
+ * A[b, i, j] = <f_i, f_j> as a k-ordered fp32 fma chain on the fp32-input MFMA (|A - exact| ~ 1e-7; A is bitwise symmetric);
+ * sums[b] = {sum, sum of squares} of the N^2 entries in fp64, folded in a fixed order.  workspace >= mvp_ncut_workspace_bytes(Bimg, N).
+ *   MVP_EINVAL: NULL feats / A / sums / workspace; Bimg, N or C out of range; ldf < N; feats or A not 4-byte, sums or workspace not
+ *   8-byte aligned; workspace too short.
+ * mvp_ncut_threshold: tau[b] = the fixed point of Lloyd's iteration for two centres on the N^2 entries of A[b], started from
+ * mean -+ std (from sums): a round assigns a to the upper cluster iff a > (c0 + c1) / 2 and replaces the centres by the cluster means
+ * (fp64 sums); it stops when the upper count repeats (the clusters are nested, so that is the assignment repeating), when a cluster is
+ * empty (the centres of the round before stand), or after max_rounds; tau = (c0 + c1) / 2.  bits [Bimg, N, ceil(N / 32)] uint32: bit
+ * (j & 31) of word j >> 5 of row i = [A[i, j] > tau], the bits beyond column N - 1 zero; deg [Bimg, N] fp64 =
+ * cnt + eps (N - cnt) from the integer row counts; rounds (optional [Bimg] int32) = rounds run.  One workgroup per image.
+ *   MVP_EINVAL: NULL A / sums / tau / bits / deg; Bimg or N out of range; max_rounds <= 0; a misaligned pointer (4 bytes for A, bits
+ *   and rounds, 8 for sums, tau and deg).
+ * mvp_ncut_fiedler: with W = B + eps (1 - B) for the bit matrix B and D = diag(deg), the second-largest eigenpair (theta, y) of
+ * S = D^-1/2 W D^-1/2, i.e. the second-smallest generalised pair (D - W) v = lambda D v with lambda = 1 - theta, v = D^-1/2 y.  One
+ * workgroup per image, the image's bit matrix resident in LDS; block subspace iteration (4 vectors, fp32) on (I + S) / 2 with the top
+ * pair (D^1/2 1, 1) deflated and a Rayleigh-Ritz step in fp64 every round; W is applied as (1 - eps) (B x) + eps sum(x).
+ *   v [Bimg, N] fp32, scaled so that |D^1/2 v| = 1 up to rounding, sign: the entry of largest |v| is positive (lowest index on ties);
+ *   lambda, residual [Bimg] fp64: 1 - theta and |S y - theta y| of y = D^1/2 v / |D^1/2 v| for the v that was written, in fp64;
+ *   iters [Bimg] int32 = rounds run; converged [Bimg] bytes = 1 iff residual <= r_tol and residual <= mix_tol * (theta - theta_3)
+ *   (theta_3 = the next Ritz value: residual / gap bounds the admixture of the neighbouring eigenvector) within max_iters rounds.
+ *   MVP_EINVAL: a NULL pointer other than active; Bimg or N out of range; max_iters <= 0; r_tol or mix_tol not > 0; a misaligned
+ *   pointer (4 bytes for bits, v and iters, 8 for deg, lambda and residual).
+ * mvp_ncut_partition: from v [Bimg, h * w] (any sign): bipartition = v > mean(v) (fp64 mean); seed0 = argmax |v|; nc = foreground
+ * corners (0, w - 1, (h - 1) w, N - 1, each counted as often as it is listed); reverse = nc >= 3 or seed0 not foreground; reversed:
+ * the bipartition is complemented and seed = argmin v, else seed = argmax v (lowest index on ties everywhere); mask = the 4-connected
+ * component of the seed.  use_prev != 0 (passes >= 2): the mask is emptied when 2 |mask & prev| > |mask | prev| (IoU > 0.5) or
+ * |mask| / h / w <= 0.01.  Then pass_mask = mask (may alias prev_mask), painted |= mask (in place), union_mask = painted with its
+ * holes filled (the complement of the background 4-connected to the border), seed[b] = seed.  All [Bimg, h * w] bytes, 0 / 1.
+ *   MVP_EINVAL: NULL v / pass_mask / painted / union_mask / seed; use_prev without prev_mask; h, w <= 0 or h * w > 1024; Bimg out of
+ *   range; v or seed not 4-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_ncut_affinity_args mvp_ncut_affinity_args;
+struct mvp_ncut_affinity_args {
+  const float* feats; const uint8_t* painted; const uint8_t* active;
+  float* A; double* sums;
+  void* workspace; int64_t workspace_bytes;
+  int64_t ldf;
+  int Bimg, C, N;
+};
+typedef struct mvp_ncut_threshold_args mvp_ncut_threshold_args;
+struct mvp_ncut_threshold_args {
+  const float* A; const double* sums; const uint8_t* active;
+  double* tau; uint32_t* bits; double* deg; int32_t* rounds;
+  int Bimg, N, max_rounds;
+};
+typedef struct mvp_ncut_fiedler_args mvp_ncut_fiedler_args;
+struct mvp_ncut_fiedler_args {
+  const uint32_t* bits; const double* deg; const uint8_t* active;
+  float* v; double* lambda; double* residual; int32_t* iters; uint8_t* converged;
+  int Bimg, N, max_iters;
+  float r_tol, mix_tol;
+};
+typedef struct mvp_ncut_partition_args mvp_ncut_partition_args;
+struct mvp_ncut_partition_args {
+  const float* v; const uint8_t* prev_mask; const uint8_t* active;
+  uint8_t* pass_mask; uint8_t* painted; uint8_t* union_mask; int32_t* seed;
+  int Bimg, h, w, use_prev;
+};
+/* Workspace of mvp_ncut_affinity: the inverse column norms and one {sum, sum of squares} pair per 64 x 64 tile of A.  0 for sizes
+ * that it rejects. */
+int64_t mvp_ncut_workspace_bytes(int Bimg, int N);
+int mvp_ncut_affinity(const mvp_ncut_affinity_args*, void* stream);
+int mvp_ncut_threshold(const mvp_ncut_threshold_args*, void* stream);
+int mvp_ncut_fiedler(const mvp_ncut_fiedler_args*, void* stream);
+int mvp_ncut_partition(const mvp_ncut_partition_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution weight re-layout (per step; the probe's conv weights are trained):

@@ -36,6 +36,7 @@ extern "C" int mvp_sizeof(const char* name) {
   MVP_SZ(mvp_gather_rows_args) MVP_SZ(mvp_relpos_terms_args) MVP_SZ(mvp_attention_relpos_args) MVP_SZ(mvp_knn_ratio_args)
   MVP_SZ(mvp_bn_act_args) MVP_SZ(mvp_bce_loss_args) MVP_SZ(mvp_binary_counts_args) MVP_SZ(mvp_pointcloud_sample_args)
   MVP_SZ(mvp_twoafc_args)
+  MVP_SZ(mvp_ncut_affinity_args) MVP_SZ(mvp_ncut_threshold_args) MVP_SZ(mvp_ncut_fiedler_args) MVP_SZ(mvp_ncut_partition_args)
 #undef MVP_SZ
   return -1;
 }

@@ -200,6 +200,26 @@ class TwoafcArgs(Struct, c_name="mvp_twoafc_args"):  # pooled cosine scoring of 
                 ("workspace", _vp), ("workspace_bytes", _i64), ("ld", _i64), ("B", _i), ("C", _i), ("HW", _i), ("accumulate", _i)]
 
 
+class NcutAffinityArgs(Struct, c_name="mvp_ncut_affinity_args"):  # MaskCut: normalised, painted-out patch affinity (added within ABI 8)
+    _fields_ = [("feats", _vp), ("painted", _vp), ("active", _vp), ("A", _vp), ("sums", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+                ("ldf", _i64), ("Bimg", _i), ("C", _i), ("N", _i)]
+
+
+class NcutThresholdArgs(Struct, c_name="mvp_ncut_threshold_args"):  # MaskCut: 2-means threshold, bit matrix, degrees (added within ABI 8)
+    _fields_ = [("A", _vp), ("sums", _vp), ("active", _vp), ("tau", _vp), ("bits", _vp), ("deg", _vp), ("rounds", _vp),
+                ("Bimg", _i), ("N", _i), ("max_rounds", _i)]
+
+
+class NcutFiedlerArgs(Struct, c_name="mvp_ncut_fiedler_args"):  # MaskCut: LDS-resident normalised-cut eigen-solver (added within ABI 8)
+    _fields_ = [("bits", _vp), ("deg", _vp), ("active", _vp), ("v", _vp), ("lambda", _vp), ("residual", _vp), ("iters", _vp),
+                ("converged", _vp), ("Bimg", _i), ("N", _i), ("max_iters", _i), ("r_tol", _f), ("mix_tol", _f)]
+
+
+class NcutPartitionArgs(Struct, c_name="mvp_ncut_partition_args"):  # MaskCut: bipartition, seed component, painting (added within ABI 8)
+    _fields_ = [("v", _vp), ("prev_mask", _vp), ("active", _vp), ("pass_mask", _vp), ("painted", _vp), ("union_mask", _vp), ("seed", _vp),
+                ("Bimg", _i), ("h", _i), ("w", _i), ("use_prev", _i)]
+
+
 class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -352,6 +372,11 @@ SYMBOLS = {
     "mvp_pointcloud_sample": PointcloudSampleArgs,
     "mvp_twoafc_score": TwoafcArgs,
     "mvp_twoafc_workspace_bytes": None,
+    "mvp_ncut_workspace_bytes": None,
+    "mvp_ncut_affinity": NcutAffinityArgs,
+    "mvp_ncut_threshold": NcutThresholdArgs,
+    "mvp_ncut_fiedler": NcutFiedlerArgs,
+    "mvp_ncut_partition": NcutPartitionArgs,
 }
 
 # the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)
@@ -371,6 +396,7 @@ SIGNATURES = {
     "mvp_gemm_tn_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "mvp_knn_workspace_bytes": (_i64, [_i, _i, _i]),
     "mvp_twoafc_workspace_bytes": (_i64, [_i, _i, _i]),
+    "mvp_ncut_workspace_bytes": (_i64, [_i, _i]),
 }
 
 _lib: Optional[C.CDLL] = None

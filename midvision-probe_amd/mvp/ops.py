@@ -561,3 +561,36 @@ def binary_counts(pred, gt, counts, G, n, threshold=0.5) -> None:
     """counts [G, 4] int64 = TP, FP, FN, TN of (pred > threshold) against gt in {0, 1}, pred / gt [G, n]: mvp_binary_counts."""
     a = lib.BinaryCountsArgs(lib.ptr(pred), lib.ptr(gt), lib.ptr(counts), G, n, threshold)
     _traced("hbm", "binary_counts", 0, float(G * n * 8), lambda: lib.call("mvp_binary_counts", a))
+
+
+def ncut_workspace_bytes(Bimg: int, N: int) -> int:
+    return int(lib.load().mvp_ncut_workspace_bytes(Bimg, N))
+
+
+def ncut_affinity(feats, A, sums, workspace, Bimg, Cdim, N, ldf=None, painted=None, active=None) -> None:
+    """A [Bimg, N, N] fp32 = the Gram matrix of the L2-normalised, painted-out columns of feats [Bimg, C, ldf] and sums [Bimg, 2] fp64
+    (sum, sum of squares of A's entries): mvp_ncut_affinity."""
+    a = lib.NcutAffinityArgs(lib.ptr(feats), lib.ptr(painted), lib.ptr(active), lib.ptr(A), lib.ptr(sums), lib.ptr(workspace),
+                             workspace.numel() * workspace.element_size(), N if ldf is None else ldf, Bimg, Cdim, N)
+    _traced("mfma", "ncut_affinity", 0, 2.0 * Bimg * N * N * Cdim, lambda: lib.call("mvp_ncut_affinity", a))
+
+
+def ncut_threshold(A, sums, tau, bits, deg, Bimg, N, max_rounds=64, rounds=None, active=None) -> None:
+    """tau [Bimg] fp64 (Lloyd's fixed point), bits [Bimg, N, ceil(N / 32)] int32 words of A > tau, deg [Bimg, N] fp64: mvp_ncut_threshold."""
+    a = lib.NcutThresholdArgs(lib.ptr(A), lib.ptr(sums), lib.ptr(active), lib.ptr(tau), lib.ptr(bits), lib.ptr(deg), lib.ptr(rounds),
+                              Bimg, N, max_rounds)
+    _traced("hbm", "ncut_threshold", 0, float(Bimg * N * N * 4), lambda: lib.call("mvp_ncut_threshold", a))
+
+
+def ncut_fiedler(bits, deg, v, lam, residual, iters, converged, Bimg, N, max_iters, r_tol, mix_tol, active=None) -> None:
+    """The second-smallest generalised eigenvector of (D - W) v = lambda D v per image, solved out of LDS: mvp_ncut_fiedler."""
+    a = lib.NcutFiedlerArgs(lib.ptr(bits), lib.ptr(deg), lib.ptr(active), lib.ptr(v), lib.ptr(lam), lib.ptr(residual), lib.ptr(iters),
+                            lib.ptr(converged), Bimg, N, max_iters, r_tol, mix_tol)
+    _traced("lds", "ncut_fiedler", 0, float(Bimg * N * N), lambda: lib.call("mvp_ncut_fiedler", a))
+
+
+def ncut_partition(v, pass_mask, painted, union_mask, seed, Bimg, h, w, prev_mask=None, use_prev=False, active=None) -> None:
+    """Bipartition, corner rule, seed component, rejection rule, painting and hole-filled union of one pass: mvp_ncut_partition."""
+    a = lib.NcutPartitionArgs(lib.ptr(v), lib.ptr(prev_mask), lib.ptr(active), lib.ptr(pass_mask), lib.ptr(painted), lib.ptr(union_mask),
+                              lib.ptr(seed), Bimg, h, w, int(use_prev))
+    _traced("lds", "ncut_partition", 0, float(Bimg * h * w), lambda: lib.call("mvp_ncut_partition", a))
