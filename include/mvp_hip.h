@@ -93,6 +93,9 @@ typedef struct {
                                 Added within 8: mvp_ncut_affinity, mvp_ncut_threshold, mvp_ncut_fiedler, mvp_ncut_partition and
                                 mvp_ncut_workspace_bytes (MaskCut: thresholded patch affinity, LDS-resident normalised-cut solver, partition);
                                 new exports with their own tagged argument structs, no existing struct changed.
+                                Added within 8: mvp_dwconv7_ln_fwd, mvp_grn_stats, mvp_grn_apply and mvp_grn_workspace_bytes (ConvNeXt / ConvNeXt V2
+                                blocks: depthwise 7x7 + LayerNorm, global response normalisation); new exports with their own tagged argument
+                                structs, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -1084,6 +1087,56 @@ int mvp_mask_split(const mvp_mask_split_args*, void* stream);
 
 int64_t mvp_gemm_tn_workspace_bytes(int Cout, int Cin, int kh, int kw, int splits);
 int mvp_gemm_tn_conv(const mvp_gemm_tn_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * ConvNeXt block, first half: depthwise 7x7 convolution (stride 1, zero padding 3) + LayerNorm over the channels on a
+ * channels-last fp32 map, written as the A operand of the block's fc1 GEMM.  Replaces what evals/models/convnext.py:87-91 runs
+ * inside `self.visual.stages` for every block: timm ConvNeXtBlock.conv_dw + .norm (transformers ConvNextLayer.dwconv + .layernorm).
+ *   y[b, y, x, c] = bias[c] + sum_{ky, kx} weight[c, ky, kx] * x[b, y + ky - 3, x + kx - 3, c]      (taps outside the image: zero,
+ *   at the seam between two images of a batch too), taps summed ky-major, then kx, the bias last, in fp32;
+ *   out[b, y, x, :] = LayerNorm_C(y[b, y, x, :]) * gamma + beta, two-pass (mean, then the centred variance) like mvp_layernorm_fwd.
+ * The same inputs give the same bits.  C % 32 == 0, 32 <= C <= 2048, any B, H, W >= 1 (maps smaller than the window included);
+ * anything else is MVP_EINVAL before any launch.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_dwconv7_ln_args mvp_dwconv7_ln_args;
+struct mvp_dwconv7_ln_args {
+  const float* x;                     /* [B, H, W, ldx] fp32 channels-last, channels 0 .. C-1 of every pixel are read; 16-byte aligned */
+  const float* weight;                /* [C, 7, 7] fp32 (nn.Conv2d(C, C, 7, padding=3, groups=C).weight)                             */
+  const float* bias;                  /* [C]                                                                                         */
+  const float* gamma; const float* beta; /* [C] LayerNorm weight / bias                                                              */
+  mvp_bf16* out_hi; mvp_bf16* out_lo; /* [B*H*W, C] pair as mvp_layernorm_args writes it (lo may be NULL; both NULL needs out_f32)   */
+  float* out_f32;                     /* optional fp32 copy [B*H*W, C], or NULL (must not alias x: neighbours read x)                */
+  int B, H, W, C;
+  int ldx;                            /* pixel stride of x, elements: >= C, % 4 == 0                                                 */
+  float eps;
+  int out_layout;                     /* MVP_PAIR_SEPARATE or MVP_PAIR_A_ILV32, as mvp_layernorm_args.out_layout                     */
+  int out_f16;                        /* 1: the pair is the activation operand of MVP_PREC_F16X2, as mvp_layernorm_args.out_f16      */
+};
+int mvp_dwconv7_ln_fwd(const mvp_dwconv7_ln_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * ConvNeXt V2's global response normalisation on the fc1 output h [B, HW, C4] fp32 (timm GlobalResponseNormMlp.grn /
+ * transformers ConvNextV2GRN, run per block by evals/models/convnext.py:87-91 for the fcmae checkpoint, :42-47):
+ *   mvp_grn_stats:  G[b, c] = sqrt(sum_hw h[b, hw, c]^2)  (fp64 partial sums folded in a fixed order),  N[b, c] = G[b, c] / (mean_c G[b, :] + 1e-6)
+ *   mvp_grn_apply:  out = gamma[c] * (h * N[b, c]) + beta[c] + h, written as the A operand pair of fc2 (and / or fp32)
+ * Both are plain launches on `stream`: no host synchronisation between them.  C4 % 8 == 0 (% 32 for MVP_PAIR_A_ILV32).
+ * workspace (mvp_grn_stats): >= mvp_grn_workspace_bytes(B, HW, C4) bytes, 8-byte aligned; it needs no initialisation.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_grn_args mvp_grn_args;
+struct mvp_grn_args {
+  const float* h;                     /* [B, HW, C4] fp32                                                                            */
+  const float* gamma; const float* beta; /* [C4] (mvp_grn_apply)                                                                     */
+  float* G;                           /* [B, C4] out of mvp_grn_stats                                                                */
+  float* N;                           /* [B, C4] out of mvp_grn_stats, in of mvp_grn_apply                                           */
+  mvp_bf16* out_hi; mvp_bf16* out_lo; /* [B*HW, C4] bf16 pair (mvp_grn_apply; lo may be NULL)                                        */
+  float* out_f32;                     /* optional fp32 copy (may be h itself), or NULL                                               */
+  void* workspace; int64_t workspace_bytes;
+  int B, HW, C4;
+  int out_layout;                     /* MVP_PAIR_SEPARATE or MVP_PAIR_A_ILV32                                                       */
+};
+int64_t mvp_grn_workspace_bytes(int B, int HW, int C4);
+int mvp_grn_stats(const mvp_grn_args*, void* stream);
+int mvp_grn_apply(const mvp_grn_args*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ extern "C" int mvp_sizeof(const char* name) {
   MVP_SZ(mvp_bn_act_args) MVP_SZ(mvp_bce_loss_args) MVP_SZ(mvp_binary_counts_args) MVP_SZ(mvp_pointcloud_sample_args)
   MVP_SZ(mvp_twoafc_args)
   MVP_SZ(mvp_ncut_affinity_args) MVP_SZ(mvp_ncut_threshold_args) MVP_SZ(mvp_ncut_fiedler_args) MVP_SZ(mvp_ncut_partition_args)
+  MVP_SZ(mvp_dwconv7_ln_args) MVP_SZ(mvp_grn_args)
 #undef MVP_SZ
   return -1;
 }

@@ -3,6 +3,7 @@ no longer exist and raises ImportError; hydra only needs the sub-modules to be i
 from . import probes  # noqa: F401
 from .beit_v2 import BEiTV2  # noqa: F401
 from .clip import CLIP  # noqa: F401
+from .convnext import ConvNext  # noqa: F401
 from .croco import CROCO  # noqa: F401
 from .crocov2 import CROCOV2  # noqa: F401
 from .dino import DINO  # noqa: F401

@@ -54,8 +54,17 @@ class _DPTViT(torch.autograd.Function):
         Hd = params[0].shape[0]
         k = params[8].shape[-1]
         Cout = params[-2].shape[0]
-        if C % 128 or Hd % 128:
-            raise lib.MvpError(f"DPT on the HIP path needs feature and hidden channels that are multiples of 128 (got {C}, {Hd})")
+        # per-tap input widths (conv_i.weight is [Hd, C_i, 1, 1]): four equal ones for a ViT, a ConvNeXt's stage widths otherwise
+        Cs = [int(params[2 * i].shape[1]) for i in range(4)]
+        offs = [sum(Cs[:i]) for i in range(4)]
+        if sum(Cs) != pack.Ctot:
+            raise lib.MvpError(f"DPT: the packed features hold {pack.Ctot} channels, the input convs expect {Cs}")
+        if len(set(Cs)) == 1:
+            if C % 128 or Hd % 128:
+                raise lib.MvpError(f"DPT on the HIP path needs feature and hidden channels that are multiples of 128 (got {C}, {Hd})")
+        elif any(c % 64 for c in Cs) or Hd % 128:
+            raise lib.MvpError(f"DPT on the HIP path with per-tap widths needs feature channels that are multiples of 64 and hidden channels "
+                               f"that are multiples of 128 (got {Cs}, {Hd})")
         K4 = _up(Cout, 4)
         M0, H1, W1 = B * h * w, 2 * h, 2 * w
         M1, H2, W2 = B * H1 * W1, 8 * h, 8 * w
@@ -65,10 +74,10 @@ class _DPTViT(torch.autograd.Function):
         # ---- conv_i (1x1) at token resolution on the packed features, then nearest x2
         u = []
         for i in range(4):
-            wi = ops.split_bf16(det[2 * i].reshape(Hd, C).float().contiguous(), pr)
+            wi = ops.split_bf16(det[2 * i].reshape(Hd, Cs[i]).float().contiguous(), pr)
             f = torch.empty(M0, Hd, dtype=torch.float32, device=dev)
-            a = (pack.tok[0][:, i * C:], pack.tok[1][:, i * C:] if pack.tok[1] is not None else None)
-            ops.gemm(a, wi, M0, Hd, C, bias=det[2 * i + 1].float().contiguous(), out_f32=f, precision=pr, lda=pack.Cpad)
+            a = (pack.tok[0][:, offs[i]:], pack.tok[1][:, offs[i]:] if pack.tok[1] is not None else None)
+            ops.gemm(a, wi, M0, Hd, Cs[i], bias=det[2 * i + 1].float().contiguous(), out_f32=f, precision=pr, lda=pack.Cpad)
             # (fp32, pair) at H1 x W1, and the COARSE pair: a 3x3 unit's first conv reads the x2 map through its coarse tap products
             u.append(cv.upsample_nearest(f, B, h, w, Hd, 2, precision=pr, want_pair=(k != 3)) + (ops.split_bf16(f, pr) if k == 3 else None,))
 
@@ -116,6 +125,7 @@ class _DPTViT(torch.autograd.Function):
         cv.conv_gemm(h0P, g3, cv.pack_weight(w2, 0, pr, pad_cout_to=K4), K4, bias=b2p, out_f32=logits, precision=pr)
 
         ctx.pack, ctx.pr, ctx.dims = pack, pr, (B, h, w, C, Hd, k, Cout, K4)
+        ctx.Cs = Cs
         ctx.saved_rcu, ctx.o0P, ctx.h0P, ctx.m0 = saved_rcu, o0P, h0P, m0
         ctx.generation = pack.generation
         ctx.param_refs = params  # the Parameter objects themselves: their FlatAdamW gradient slots are looked up in backward
@@ -228,15 +238,25 @@ class _DPTViT(torch.autograd.Function):
         # NB: for unit==1 the loop leaves gy untouched, which is exactly d(sum)/d(out) = identity.
 
         # ---- conv_i (1x1): adjoint of nearest x2, then dW over the packed feature tokens
-        g0 = cv.geom(B, h, w, C, 1, 1, 1, 0)
+        Cs = ctx.Cs
+        uniform = len(set(Cs)) == 1
+        # per-tap widths (multiples of 64): the TN kernel takes input channels in multiples of 128, so every tap's weight gradient is
+        # formed over the whole packed row (Cpad columns, a multiple of 128) and its own columns are kept
+        g0 = cv.geom(B, h, w, C if uniform else pack.Cpad, 1, 1, 1, 0)
         for i in range(4):
             if g_u[i][1]:
                 gfF, gfP = g_u[i][0], ops.split_bf16(g_u[i][0], pr)
             else:
                 gfF, gfP = cv.upsample_nearest(g_u[i][0], B, h, w, Hd, 2, precision=pr, backward=True)
             grads[2 * i] = new_like(det[2 * i])
-            x = (pack.tok[0][:, i * C:], pack.tok[1][:, i * C:] if pack.tok[1] is not None else None)
-            cv.conv_dw(gfP, Hd, x, pack.Cpad, g0, Hd, grads[2 * i], precision=pr)
+            if uniform:
+                x = (pack.tok[0][:, i * C:], pack.tok[1][:, i * C:] if pack.tok[1] is not None else None)
+                cv.conv_dw(gfP, Hd, x, pack.Cpad, g0, Hd, grads[2 * i], precision=pr)
+            else:
+                full = torch.empty(Hd, pack.Cpad, 1, 1, dtype=torch.float32, device=dev)
+                cv.conv_dw(gfP, Hd, pack.tok, pack.Cpad, g0, Hd, full, precision=pr)
+                off = sum(Cs[:i])
+                grads[2 * i].copy_(full[:, off:off + Cs[i]])
             grads[2 * i + 1] = bias_grad(gfF, Hd)
         return (None, None, *grads)
 

@@ -220,6 +220,16 @@ class NcutPartitionArgs(Struct, c_name="mvp_ncut_partition_args"):  # MaskCut: b
                 ("Bimg", _i), ("h", _i), ("w", _i), ("use_prev", _i)]
 
 
+class Dwconv7LnArgs(Struct, c_name="mvp_dwconv7_ln_args"):  # ConvNeXt: depthwise 7x7 + LayerNorm -> fc1's A operand (added within ABI 8)
+    _fields_ = [("x", _vp), ("weight", _vp), ("bias", _vp), ("gamma", _vp), ("beta", _vp), ("out_hi", _vp), ("out_lo", _vp), ("out_f32", _vp),
+                ("B", _i), ("H", _i), ("W", _i), ("C", _i), ("ldx", _i), ("eps", _f), ("out_layout", _i), ("out_f16", _i)]
+
+
+class GrnArgs(Struct, c_name="mvp_grn_args"):  # ConvNeXt V2: global response normalisation, statistics and apply (added within ABI 8)
+    _fields_ = [("h", _vp), ("gamma", _vp), ("beta", _vp), ("G", _vp), ("N", _vp), ("out_hi", _vp), ("out_lo", _vp), ("out_f32", _vp),
+                ("workspace", _vp), ("workspace_bytes", _i64), ("B", _i), ("HW", _i), ("C4", _i), ("out_layout", _i)]
+
+
 class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -377,6 +387,10 @@ SYMBOLS = {
     "mvp_ncut_threshold": NcutThresholdArgs,
     "mvp_ncut_fiedler": NcutFiedlerArgs,
     "mvp_ncut_partition": NcutPartitionArgs,
+    "mvp_dwconv7_ln_fwd": Dwconv7LnArgs,
+    "mvp_grn_workspace_bytes": None,
+    "mvp_grn_stats": GrnArgs,
+    "mvp_grn_apply": GrnArgs,
 }
 
 # the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)
@@ -397,6 +411,7 @@ SIGNATURES = {
     "mvp_knn_workspace_bytes": (_i64, [_i, _i, _i]),
     "mvp_twoafc_workspace_bytes": (_i64, [_i, _i, _i]),
     "mvp_ncut_workspace_bytes": (_i64, [_i, _i]),
+    "mvp_grn_workspace_bytes": (_i64, [_i, _i, _i]),
 }
 
 _lib: Optional[C.CDLL] = None

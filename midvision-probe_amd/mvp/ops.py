@@ -594,3 +594,47 @@ def ncut_partition(v, pass_mask, painted, union_mask, seed, Bimg, h, w, prev_mas
     a = lib.NcutPartitionArgs(lib.ptr(v), lib.ptr(prev_mask), lib.ptr(active), lib.ptr(pass_mask), lib.ptr(painted), lib.ptr(union_mask),
                               lib.ptr(seed), Bimg, h, w, int(use_prev))
     _traced("lds", "ncut_partition", 0, float(Bimg * h * w), lambda: lib.call("mvp_ncut_partition", a))
+
+
+def dwconv7_ln(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out, B: int, H: int, W: int,
+               Cdim: int, eps: float, *, ldx: Optional[int] = None, out_f32: Optional[torch.Tensor] = None, out_f16: bool = False) -> None:
+    """Depthwise 7x7 (padding 3) + LayerNorm over the channels of the channels-last fp32 map ``x`` [B, H, W, ldx] -> ``out`` (a Pair, an
+    IlvPair or None) [B*H*W, C] and / or ``out_f32``: mvp_dwconv7_ln_fwd.  ``weight`` [C, 7, 7] (or the conv's [C, 1, 7, 7])."""
+    ilv = isinstance(out, IlvPair)
+    if ilv:
+        out = (out.t, None)
+    elif out is None:
+        out = (None, None)
+    a = lib.Dwconv7LnArgs(lib.ptr(x), lib.ptr(weight), lib.ptr(bias), lib.ptr(gamma), lib.ptr(beta), lib.ptr(out[0]), lib.ptr(out[1]),
+                          lib.ptr(out_f32), B, H, W, Cdim, Cdim if ldx is None else ldx, eps, lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE,
+                          1 if out_f16 else 0)
+    # algorithmic HBM bytes: the map read once, the pair written once
+    _traced("hbm", "dwconv7_ln_kernel", 0, float(B * H * W * Cdim * 8), lambda: lib.call("mvp_dwconv7_ln_fwd", a))
+
+
+def grn_workspace_bytes(B: int, HW: int, C4: int) -> int:
+    return int(lib.load().mvp_grn_workspace_bytes(B, HW, C4))
+
+
+def _grn_args(h, B, HW, C4, *, G=None, N=None, gamma=None, beta=None, out=None, out_f32=None, workspace=None):
+    ilv = isinstance(out, IlvPair)
+    if ilv:
+        out = (out.t, None)
+    elif out is None:
+        out = (None, None)
+    return lib.GrnArgs(lib.ptr(h), lib.ptr(gamma), lib.ptr(beta), lib.ptr(G), lib.ptr(N), lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(out_f32),
+                       lib.ptr(workspace), workspace.numel() * workspace.element_size() if workspace is not None else 0, B, HW, C4,
+                       lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE)
+
+
+def grn_stats(h: torch.Tensor, G: torch.Tensor, N: torch.Tensor, workspace: torch.Tensor, B: int, HW: int, C4: int) -> None:
+    """G [B, C4] = the L2 norm of h [B, HW, C4] over HW, N = G / (mean_c G + 1e-6): mvp_grn_stats (ConvNeXt V2's GRN)."""
+    a = _grn_args(h, B, HW, C4, G=G, N=N, workspace=workspace)
+    _traced("hbm", "grn_stats", 0, float(B * HW * C4 * 4), lambda: lib.call("mvp_grn_stats", a))
+
+
+def grn_apply(h: torch.Tensor, N: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out, B: int, HW: int, C4: int,
+              out_f32: Optional[torch.Tensor] = None) -> None:
+    """gamma (h N) + beta + h -> ``out`` (a Pair, an IlvPair or None) and / or ``out_f32``: mvp_grn_apply."""
+    a = _grn_args(h, B, HW, C4, N=N, gamma=gamma, beta=beta, out=out, out_f32=out_f32)
+    _traced("hbm", "grn_apply", 0, float(B * HW * C4 * 8), lambda: lib.call("mvp_grn_apply", a))

@@ -31,7 +31,10 @@ MODELS = {"dino_b16": ("dino", "vitb16", "dense"), "dinov2_b14": ("dinov2", "vit
           "beit-v2_vitb16": ("beit_v2", "vitb16", "dense"),
           # windowed blocks: two row gathers, fp32 qkv + mvp_relpos_terms, attention with the decomposed bias (SAM); no tap norm
           # (the wrapper refuses add_norm); --size 512 / 1024 for the sizes the encoder is meant for
-          "sam_base": ("sam", "vit_b", "dense"), "sam_large": ("sam", "vit_l", "dense")}
+          "sam_base": ("sam", "vit_b", "dense"), "sam_large": ("sam", "vit_l", "dense"),
+          # ConvNeXt-B / ConvNeXt V2-B: four taps of widths 128 ... 1024 resized to one 14 x 14 grid; bf16x3 whatever --precision says, no tap
+          # norm (the wrapper refuses add_norm), serial forwards (the engine is not pipelined) (ConvNeXt)
+          "convnext_in22k": ("convnext", "in22k", "dense"), "convnext_fcmae": ("convnext", "fcmae_ft_in22k_in1k_384", "dense")}
 
 
 def build(name, precision, dev):
@@ -52,6 +55,10 @@ def build(name, precision, dev):
             from evals.models.sam import SAM
 
             model = SAM(mn, output=out, return_multilayer=True, precision=precision).to(dev)
+        elif dn == "convnext":
+            from evals.models.convnext import ConvNext
+
+            model = ConvNext("convnext_base", mn, output=out, return_multilayer=True, precision=precision).to(dev)
         elif dn == "beit_v2":
             from evals.models.beit_v2 import BEiTV2
 
