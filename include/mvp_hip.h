@@ -96,6 +96,9 @@ typedef struct {
                                 Added within 8: mvp_dwconv7_ln_fwd, mvp_grn_stats, mvp_grn_apply and mvp_grn_workspace_bytes (ConvNeXt / ConvNeXt V2
                                 blocks: depthwise 7x7 + LayerNorm, global response normalisation); new exports with their own tagged argument
                                 structs, no existing struct changed.
+                                Added within 8: mvp_crf_filter, mvp_crf_update and mvp_mask_finish (dense-CRF refinement of the MaskCut masks: exact
+                                all-pairs Gaussian filtering, mean-field update, hole filling / IoU rule / union); new exports with their own tagged
+                                argument structs, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -907,6 +910,90 @@ int mvp_ncut_affinity(const mvp_ncut_affinity_args*, void* stream);
 int mvp_ncut_threshold(const mvp_ncut_threshold_args*, void* stream);
 int mvp_ncut_fiedler(const mvp_ncut_fiedler_args*, void* stream);
 int mvp_ncut_partition(const mvp_ncut_partition_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; new exports with their own tagged argument structs, no existing struct changed.)
+ * Dense CRF: the refinement the reference applies to every MaskCut bipartition (evals/models/crf.py::densecrf and
+ * maskcut_processor.py:376-404), with the CRF's two message-passing sums evaluated exactly over all pixel pairs.  The model:
+ *
+ * Given an image `I` (uint8 RGB, H × W) and a binary mask `m` (H × W; `crf.py` bilinearly resizes the two logit planes `(1−m, m)` to
+ * H × W when sizes differ, an identity in the processor):
+ *
+ * - **Unary.** `p_l(i) = softmax_l(1−m_i, m_i)`, that is `e/(1+e)` for the pixel's own label and `1/(1+e)` for the other.
+ *   `U_l(i) = −log p_l(i)`. `unary_from_softmax` clips at 1e-5, which is never reached here.
+ * - **Kernels.** Both include `j = i`.
+ *   - `k_g(i,j) = exp(−(Δx²+Δy²)/(2·3²))`, weight 7.
+ *   - `k_b(i,j) = exp(−(Δx²+Δy²)/(2·50²) − (Δr²+Δg²+Δb²)/(2·5²))`, weight 10.
+ *   - These are `POS_W`, `POS_XY_STD`, `Bi_W`, `Bi_XY_STD`, `Bi_RGB_STD` of `crf.py`.
+ * - **Symmetric normalisation.** `n(i) = (Σ_j k(i,j) + 1e-20)^(−1/2)`. The filtered field is `n(i)·Σ_j k(i,j)·n(j)·Q_l(j)`.
+ * - **Mean field.** `Q⁰ = p`. For t = 1…10 (`MAX_ITER`): `a_l = −U_l + 7·(filtered_g Q_l) + 10·(filtered_b Q_l)` with Potts
+ *   compatibility, then `Q = softmax_l(a)`.
+ * - **MAP.** `MAP(i) = 1` iff `Q_1(i) > Q_0(i)`. Ties go to 0.
+ *
+ * With two labels one field per object is kept: Q_0 = 1 - Q_1, so per image K·1 (-> n) and K·n are filtered once and K·(n Q_1) once
+ * per iteration, all objects of an image as the F fields of one pass.  `active` (optional [B] bytes; NULL = all) as for MaskCut: the
+ * workgroups of an image whose byte is 0 return at once and none of its outputs is written.  No floating-point atomics; two calls
+ * give the same bits.
+ *
+ * mvp_crf_filter: out[b, f, i] = sum over ALL pixels j of image b of w(i, j) in[b, f, j],
+ *     w(i, j) = exp(-(dx^2 + dy^2) inv_var_xy / 2 - (dr^2 + dg^2 + db^2) inv_var_rgb / 2)      (inv_var = 1 / sigma^2)
+ * rgb [B, H, W, 3] bytes; in / out: field f of image b at element b * stride + f * H * W, F <= 8 fields (fields >= F are neither read
+ * nor written); in == NULL stands for the all-ones field.  inv_var_rgb == 0 gives the spatial kernel (rgb is then not read).  The
+ * differences are formed directly (exact integers in fp32, no |a|^2 + |b|^2 - 2ab expansion), the weight is one hardware exp2 with
+ * log2(e) folded into the constants.  Lanes own the pixels of a 16 x 16 target tile, the 16 x 16 source tiles pass through LDS and are
+ * read as broadcasts; each source row's 16 terms are summed in fp32 and the row sums are folded into an fp64 accumulator in row and
+ * tile order, rounded once to fp32 at the end.  A tile pair whose closest pixels already give a weight <= 2^-40 is skipped: every sum
+ * of a non-negative field changes by less than H W 2^-40 times the field's maximum (sigma = 3 makes the kernel local: 23 pixels).
+ *   MVP_EINVAL: NULL rgb / out; B not in 1..65535; F not in 1..8; H or W not in 1..4096 or H W > 2^22; a stride < F H W; inv_var_xy not
+ *   > 0 or inv_var_rgb < 0 (or not finite); in / out not 4-byte aligned.
+ * mvp_crf_update: pointwise, fp64 arithmetic on fp32 fields; N = H W; the [B, F, N] buffers (mask, filt_*, q, x_*, map) hold field f
+ * of image b at element b * stride + f * N, the [B, N] buffers (norm_*, ones_*) are dense.
+ *   MVP_CRF_NORMALISE: norm_k <- (norm_k + 1e-20)^(-1/2) in place (norm_k holding K_k·1 on entry), k = g, b.
+ *   MVP_CRF_INIT:      q = Q_1^0 = 1 / (1 + exp(1 - 2 mask)) (mask in [0, 1]: the resized logit plane, 0 / 1 in the processor).
+ *   MVP_CRF_STEP:      q = 1 / (1 + exp(-(a_1 - a_0))),  a_1 - a_0 = U_0 - U_1 + w_g n_g (2 filt_g - ones_g) + w_b n_b (2 filt_b - ones_b)
+ *                      with filt_k = K_k·(n_k Q_1) and ones_k = K_k·n_k (U from mask, clipped at 1e-5 like unary_from_softmax).
+ *   INIT and STEP also write x_k = n_k q (the next filter inputs) and, when map != NULL, map = [a_1 - a_0 > 0] as bytes.
+ *   MVP_EINVAL: a NULL pointer the mode needs; B not in 1..65535; F not in 1..8; N not in 1..2^22; stride < F N; an unknown mode; a
+ *   float pointer not 4-byte aligned.
+ * mvp_mask_finish: the post-processing of process_image.  map, ref, refined: [B, F, H W] bytes (field f of image b at
+ * b * stride + f * H W, F <= 64 passes); active here is optional [B, F] bytes, one per (image, pass).  One workgroup per active (image, pass), the
+ * mask bit-packed in LDS (H * 32 * ceil(W / 32) <= 2^20 bits): A = binary_fill_holes(map) (the complement of the background that is
+ * 4-connected to the border); refined = A, or all zeros iff 2 |A & ref| < |A | ref| (IoU < 0.5 on integer counts; an empty union keeps
+ * it, like the NaN comparison of the reference); kept (optional [B, F] bytes) = 0 where it was dropped.  Then, when union_mask
+ * (optional [B, H W] bytes) is given, one workgroup per image: union_mask = binary_fill_holes(OR of the active passes' refined).
+ *   MVP_EINVAL: NULL map / ref / refined; B not in 1..65535; F not in 1..64; H, W <= 0 or H * ceil(W / 32) > 32768; stride < F H W.
+ * ---------------------------------------------------------------------------------- */
+#define MVP_CRF_NORMALISE 0
+#define MVP_CRF_INIT 1
+#define MVP_CRF_STEP 2
+typedef struct mvp_crf_filter_args mvp_crf_filter_args;
+struct mvp_crf_filter_args {
+  const uint8_t* rgb; const float* in; const uint8_t* active;
+  float* out;
+  int64_t in_stride, out_stride;
+  int B, F, H, W;
+  float inv_var_xy, inv_var_rgb;
+};
+typedef struct mvp_crf_update_args mvp_crf_update_args;
+struct mvp_crf_update_args {
+  const float* mask; const uint8_t* active;
+  float* norm_g; float* norm_b;
+  const float* ones_g; const float* ones_b; const float* filt_g; const float* filt_b;
+  float* q; float* x_g; float* x_b; uint8_t* map;
+  int64_t stride, N;
+  int B, F, mode;
+  float w_g, w_b;
+};
+typedef struct mvp_mask_finish_args mvp_mask_finish_args;
+struct mvp_mask_finish_args {
+  const uint8_t* map; const uint8_t* ref; const uint8_t* active;
+  uint8_t* refined; uint8_t* kept; uint8_t* union_mask;
+  int64_t stride;
+  int B, F, H, W;
+};
+int mvp_crf_filter(const mvp_crf_filter_args*, void* stream);
+int mvp_crf_update(const mvp_crf_update_args*, void* stream);
+int mvp_mask_finish(const mvp_mask_finish_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Convolution weight re-layout (per step; the probe's conv weights are trained):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Entry point mirroring the reference's evaluate_generic_objectness.py main (lines 337-422) on MI355X: compose the config, build the
 trainval and test sets and the backbone, run MaskCut on every image (mvp.maskcut: four launches per pass, batched, the eigen-solve out
-of LDS), print the train and test averages of F-measure / IoU / accuracy / CorLoc and append the reference's row, plus the number of
+of LDS; with +refine=dense_crf also the reference's dense-CRF post-processing of every pass, mvp.densecrf), print the train and test averages of F-measure / IoU / accuracy / CorLoc and append the reference's row, plus the number of
 host-side fallback solves, to <output_dir>/final_results_summary.csv.  Data: VOC-shaped synthetic samples (the VOC file reader, wandb
 and the plots are out of scope).
 
@@ -27,7 +27,8 @@ def main(argv):
     model = config.instantiate(cfg["backbone"]).to(dev)
     model.eval()
     fixed_size = int(cfg["dataset"].get("fixed_size", 480))
-    processor = MaskCutProcessor(backbone=model, patch_size=int(model.patch_size), tau=0.15, fixed_size=fixed_size)
+    processor = MaskCutProcessor(backbone=model, patch_size=int(model.patch_size), tau=0.15, fixed_size=fixed_size,
+                                 refine=str(cfg.get("refine", "none")))
     batch_size = int(cfg["batch_size"])
     train_avg, train_fb, n_train = maskcut.predict(processor, trainval_dataset, batch_size, dev)
     print(f"Final training average metrics: {train_avg}  ({n_train} images, {train_fb} fallback solves)")

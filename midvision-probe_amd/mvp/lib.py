@@ -230,6 +230,22 @@ class GrnArgs(Struct, c_name="mvp_grn_args"):  # ConvNeXt V2: global response no
                 ("workspace", _vp), ("workspace_bytes", _i64), ("B", _i), ("HW", _i), ("C4", _i), ("out_layout", _i)]
 
 
+class CrfFilterArgs(Struct, c_name="mvp_crf_filter_args"):  # dense CRF: exact all-pairs Gaussian filtering of F fields (added within ABI 8)
+    _fields_ = [("rgb", _vp), ("in", _vp), ("active", _vp), ("out", _vp), ("in_stride", _i64), ("out_stride", _i64),
+                ("B", _i), ("F", _i), ("H", _i), ("W", _i), ("inv_var_xy", _f), ("inv_var_rgb", _f)]
+
+
+class CrfUpdateArgs(Struct, c_name="mvp_crf_update_args"):  # dense CRF: normalisers, Q^0, one mean-field step, MAP (added within ABI 8)
+    _fields_ = [("mask", _vp), ("active", _vp), ("norm_g", _vp), ("norm_b", _vp), ("ones_g", _vp), ("ones_b", _vp), ("filt_g", _vp),
+                ("filt_b", _vp), ("q", _vp), ("x_g", _vp), ("x_b", _vp), ("map", _vp), ("stride", _i64), ("N", _i64),
+                ("B", _i), ("F", _i), ("mode", _i), ("w_g", _f), ("w_b", _f)]
+
+
+class MaskFinishArgs(Struct, c_name="mvp_mask_finish_args"):  # hole filling, IoU rule and union of the refined masks (added within ABI 8)
+    _fields_ = [("map", _vp), ("ref", _vp), ("active", _vp), ("refined", _vp), ("kept", _vp), ("union_mask", _vp), ("stride", _i64),
+                ("B", _i), ("F", _i), ("H", _i), ("W", _i)]
+
+
 class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -391,6 +407,9 @@ SYMBOLS = {
     "mvp_grn_workspace_bytes": None,
     "mvp_grn_stats": GrnArgs,
     "mvp_grn_apply": GrnArgs,
+    "mvp_crf_filter": CrfFilterArgs,
+    "mvp_crf_update": CrfUpdateArgs,
+    "mvp_mask_finish": MaskFinishArgs,
 }
 
 # the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)

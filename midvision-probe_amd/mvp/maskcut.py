@@ -6,8 +6,9 @@ dense scipy eigh and ndimage.label.  Here a pass is four launches batched over t
 on the fp32-input MFMA, a deterministic 2-means threshold that leaves a bit matrix, an eigen-solver that keeps that bit matrix in LDS,
 and the partition / painting step.  ``max(num_objects)`` passes are issued back to back without a host sync, images with fewer
 objects idle through an ``active`` byte; the union is upsampled to the mask and counted by mvp_binary_counts.  One transfer per batch
-brings the [B, 4] counts and the ``converged`` bytes.  An image whose solve did not converge on the device (near-degenerate
-lambda_2 ~ lambda_3) is done again with torch.linalg.eigh on S in fp64 on the host, re-entering at the partition launch; how many
+brings the [B, 4] counts and the ``converged`` bytes.  With ``refine="dense_crf"`` every pass's mask then goes through the reference's
+post-processing at pixel level (mvp/densecrf.py: dense CRF, hole filling, IoU rule, union) before it is counted.  An image whose
+solve did not converge on the device (near-degenerate lambda_2 ~ lambda_3) is done again with torch.linalg.eigh on S in fp64 on the host, re-entering at the partition launch; how many
 did is reported (``n_fallback``).  Deviations from the reference: INTEGRATION.md."""
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
+from . import densecrf
 from . import functional as MF
 from . import lib, ops
 from .objectness import METRICS, metrics_from_counts
@@ -25,6 +27,8 @@ R_TOL = 2e-6                 # convergence: |S y - theta y| <= R_TOL (DESIGN.md,
 MIX_TOL = 1e-3               # ... and <= MIX_TOL * (theta_2 - theta_3): the admixture of the neighbouring eigenvector
 MAX_ITERS = 1000
 LLOYD_ROUNDS = 64
+REFINE_MODES = ("none", "dense_crf")
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 CSV_HEADER = ["Model Name", "Train Avg F-measure", "Train Avg IoU", "Train Avg Accuracy", "Train Avg CorLoc", "Test Avg F-measure",
               "Test Avg IoU", "Test Avg Accuracy", "Test Avg CorLoc", "n_fallback"]
 
@@ -106,12 +110,24 @@ def host_eigenvector(bits: torch.Tensor, deg: torch.Tensor, N: int) -> torch.Ten
     return v.float()
 
 
+def keep_crf_input(crf_inputs: torch.Tensor, p: int, buf: _Buffers, act: torch.Tensor) -> None:
+    """The reference's ``bipartition_masked`` of pass p on the grid (maskcut_processor.py:278-286): the pass's mask minus the cells of the
+    earlier passes' inputs, for the images with a set ``act`` byte -> crf_inputs[:, p] ([B, P, N] bytes); the other images keep theirs."""
+    cur = buf.mask
+    if p:
+        cur = cur * (1 - crf_inputs[:, :p].amax(dim=1))
+    a = act.view(-1, 1)
+    crf_inputs[:, p] = cur * a + crf_inputs[:, p] * (1 - a)
+
+
 def maskcut_batch(feats: torch.Tensor, h: int, w: int, num_objects: Sequence[int], *, max_iters: int = MAX_ITERS, r_tol: float = R_TOL,
-                  mix_tol: float = MIX_TOL, buf: Optional[_Buffers] = None, keep_passes: bool = False):
+                  mix_tol: float = MIX_TOL, buf: Optional[_Buffers] = None, keep_passes: bool = False,
+                  crf_inputs: Optional[torch.Tensor] = None):
     """The pass loop of maskcut_forward for a batch.  feats [B, C, h*w] fp32 on the device (extract_kqv's layout), num_objects per
     image.  Issues max(num_objects) passes of the four launches without a host sync and returns
     (buf, converged [P, B] uint8 on the device, active [P, B] uint8 on the device[, per-pass copies]); buf.union holds the prediction on
-    the grid (holes filled).  ``finish_fallbacks`` then repairs the images whose solve did not converge."""
+    the grid (holes filled).  ``finish_fallbacks`` then repairs the images whose solve did not converge.  ``crf_inputs``: a zeroed
+    [B, P, h*w] byte tensor that receives every pass's CRF input (``keep_crf_input``; refinement only)."""
     if feats.dim() != 3:
         raise ValueError(f"maskcut: feats must be [B, C, h*w], got {tuple(feats.shape)}")
     B, C, N = feats.shape
@@ -137,13 +153,16 @@ def maskcut_batch(feats: torch.Tensor, h: int, w: int, num_objects: Sequence[int
         threshold(buf, active=act)
         fiedler(buf, converged[p], active=act, max_iters=max_iters, r_tol=r_tol, mix_tol=mix_tol)
         partition(buf, h, w, use_prev=p >= 1, active=act)
+        if crf_inputs is not None:
+            keep_crf_input(crf_inputs, p, buf, act)
         if keep_passes:
             kept.append({k: getattr(buf, k).clone() for k in ("A", "sums", "tau", "bits", "deg", "rounds", "v", "lam", "res", "iters", "mask",
                                                               "painted", "union", "seed")})
     return (buf, converged, active, kept) if keep_passes else (buf, converged, active)
 
 
-def finish_fallbacks(feats: torch.Tensor, h: int, w: int, num_objects: Sequence[int], buf: _Buffers, converged_host: torch.Tensor) -> int:
+def finish_fallbacks(feats: torch.Tensor, h: int, w: int, num_objects: Sequence[int], buf: _Buffers, converged_host: torch.Tensor,
+                     crf_inputs: Optional[torch.Tensor] = None) -> int:
     """Run again, pass by pass (with a host sync per pass) and with the host solve wherever the device does not converge, every image
     that has a clear ``converged`` byte in one of its passes; the other images idle and keep their results.  -> number of host solves."""
     B, N = buf.B, buf.N
@@ -158,6 +177,8 @@ def finish_fallbacks(feats: torch.Tensor, h: int, w: int, num_objects: Sequence[
     buf.painted[idx] = 0
     buf.mask[idx] = 0
     buf.union[idx] = 0
+    if crf_inputs is not None:
+        crf_inputs[idx] = 0
     n_fallback = 0
     conv = torch.ones(B, dtype=torch.uint8, device=dev)
     for p in range(max(int(num_objects[b]) for b in todo)):
@@ -173,6 +194,8 @@ def finish_fallbacks(feats: torch.Tensor, h: int, w: int, num_objects: Sequence[
                 buf.v[b].copy_(host_eigenvector(buf.bits[b], buf.deg[b], N))
                 n_fallback += 1
         partition(buf, h, w, use_prev=p >= 1, active=act)
+        if crf_inputs is not None:
+            keep_crf_input(crf_inputs, p, buf, act)
     return n_fallback
 
 
@@ -188,14 +211,32 @@ def upsampled_counts(union: torch.Tensor, h: int, w: int, gt: torch.Tensor) -> t
     return counts
 
 
+def quantise_rgb(images: torch.Tensor, rgb: Optional[torch.Tensor]) -> torch.Tensor:
+    """The uint8 image the CRF sees, [B, 3, H, W]: round(255 rgb) of ``rgb`` in [0, 1], or of ``images`` with the ImageNet normalisation undone."""
+    if rgb is None:
+        mean = torch.tensor(IMAGENET_MEAN, device=images.device, dtype=torch.float32).view(1, 3, 1, 1)
+        std = torch.tensor(IMAGENET_STD, device=images.device, dtype=torch.float32).view(1, 3, 1, 1)
+        rgb = images.float() * std + mean
+    elif tuple(rgb.shape) != tuple(images.shape):
+        raise ValueError(f"MaskCutProcessor: rgb {tuple(rgb.shape)} against images {tuple(images.shape)}")
+    return torch.round(255.0 * rgb.float()).clamp_(0.0, 255.0).to(torch.uint8)
+
+
 class MaskCutProcessor:
     """The reference's MaskCutProcessor on the HIP path.  It takes the dataset's tensors (``original_image``: already fixed_size^2 and
-    normalised) instead of opening image files, and has no dense CRF: ``crf=True`` raises."""
+    normalised) instead of opening image files.  ``refine="dense_crf"`` runs the reference's post-processing of every pass (dense CRF with
+    exact message passing, hole filling, IoU rule, union: mvp/densecrf.py) and scores at pixel level; ``refine="none"`` (the default)
+    scores the patch grid.  The reference's ``crf`` flag is not how the refinement is selected: ``crf=True`` raises."""
 
-    def __init__(self, backbone, feature_extractor_fn=None, patch_size: int = 16, tau: float = 0.15, fixed_size: int = 480, crf: bool = False):
+    def __init__(self, backbone, feature_extractor_fn=None, patch_size: int = 16, tau: float = 0.15, fixed_size: int = 480, crf: bool = False,
+                 refine: str = "none"):
         if crf:
-            raise NotImplementedError("MaskCutProcessor(crf=True): the dense CRF post-processing (pydensecrf, host side) is not part of "
-                                      "this port; crf=False is the only mode (INTEGRATION.md, MaskCut deviations)")
+            raise NotImplementedError("MaskCutProcessor(crf=True): the pydensecrf post-processing of the reference (host side, approximate) is "
+                                      'not part of this port; pass refine="dense_crf" for the exact dense CRF on the device '
+                                      "(INTEGRATION.md, MaskCut deviations)")
+        if refine not in REFINE_MODES:
+            raise ValueError(f"MaskCutProcessor: refine must be one of {REFINE_MODES}, got {refine!r}")
+        self.refine = refine
         self.backbone = backbone
         self.feature_extractor_fn = feature_extractor_fn if feature_extractor_fn is not None else self.default_feature_extractor
         self.patch_size, self.fixed_size = int(patch_size), int(fixed_size)
@@ -216,10 +257,13 @@ class MaskCutProcessor:
         self._buf, converged, _ = maskcut_batch(feats, h, w, num_pseudo_masks, buf=self._buf)
         return self._buf, converged
 
-    def process_batch(self, images: torch.Tensor, gt: torch.Tensor, num_objects: Sequence[int]):
-        """images [B, 3, S, S] on the device, gt [B, 1, H, W] 0 / 1 -> (per-image metric dicts, n_fallback)."""
+    def process_batch(self, images: torch.Tensor, gt: torch.Tensor, num_objects: Sequence[int], rgb: Optional[torch.Tensor] = None):
+        """images [B, 3, S, S] on the device, gt [B, 1, H, W] 0 / 1 -> (per-image metric dicts, n_fallback).  ``rgb`` [B, 3, S, S] in [0, 1]:
+        the image the dense CRF sees (refinement only; without it the ImageNet normalisation of ``images`` is undone)."""
         if images.shape[-1] % self.patch_size or images.shape[-2] % self.patch_size:
             raise ValueError("MaskCutProcessor: the image size must be a multiple of the patch size")
+        if self.refine != "none":
+            return self._process_batch_refined(images, gt, num_objects, rgb)
         h, w = images.shape[-2] // self.patch_size, images.shape[-1] // self.patch_size
         feats = self.feature_extractor_fn(images)
         if feats.dim() != 3 or feats.shape[-1] != h * w:
@@ -237,6 +281,42 @@ class MaskCutProcessor:
         rows = [metrics_from_counts(*host[4 * b:4 * b + 4].tolist()) for b in range(B)]
         return [{k: r[k] for k in METRICS} for r in rows], n_fallback
 
+    def _features(self, images: torch.Tensor):
+        h, w = images.shape[-2] // self.patch_size, images.shape[-1] // self.patch_size
+        feats = self.feature_extractor_fn(images)
+        if feats.dim() != 3 or feats.shape[-1] != h * w:
+            raise ValueError(f"MaskCutProcessor: the backbone must return [B, C, {h * w}] key features (return_kqv=True), got {tuple(feats.shape)}")
+        return feats.detach().contiguous().float(), h, w
+
+    def refined_union(self, images: torch.Tensor, num_objects: Sequence[int], rgb: Optional[torch.Tensor] = None):
+        """The pass loop, the fallbacks and the refinement -> (union [B, H, W] uint8 at pixel level, per-pass CRF inputs [B, P, H, W] uint8,
+        active [B, P] uint8, n_fallback), all on the device; the first is a view of mvp.densecrf's buffers."""
+        feats, h, w = self._features(images)
+        B = feats.shape[0]
+        H, W = images.shape[-2:]
+        P = max(int(k) for k in num_objects)
+        grid_inputs = torch.zeros(B, P, h * w, dtype=torch.uint8, device=feats.device)
+        self._buf, converged, active = maskcut_batch(feats, h, w, num_objects, buf=self._buf, crf_inputs=grid_inputs)
+        n_fallback = finish_fallbacks(feats, h, w, num_objects, self._buf, converged.cpu(), crf_inputs=grid_inputs)
+        with torch.no_grad():
+            up = MF.interpolate(grid_inputs.view(B, P, h, w).float(), size=(H, W), mode="nearest")  # maskcut_processor.py:279-283
+        inputs = up.to(torch.uint8)
+        pass_active = active.t().contiguous()
+        union, _, _ = densecrf.refine_and_union(quantise_rgb(images, rgb), inputs, pass_active)
+        return union, inputs, pass_active, n_fallback
+
+    def _process_batch_refined(self, images, gt, num_objects, rgb):
+        B = images.shape[0]
+        H, W = images.shape[-2:]
+        if tuple(gt.shape[-2:]) != (H, W):
+            raise ValueError(f"MaskCutProcessor(refine={self.refine!r}): gt {tuple(gt.shape)} must have the image's size {H} x {W}")
+        union, _, _, n_fallback = self.refined_union(images, num_objects, rgb)
+        counts = torch.empty(B, 4, dtype=torch.int64, device=union.device)
+        ops.binary_counts(union.reshape(B, H * W).float(), gt.detach().reshape(B, H * W).contiguous().float(), counts, B, H * W, 0.5)
+        host = counts.reshape(-1).cpu()
+        rows = [metrics_from_counts(*host[4 * b:4 * b + 4].tolist()) for b in range(B)]
+        return [{k: r[k] for k in METRICS} for r in rows], n_fallback
+
 
 def predict(processor: MaskCutProcessor, dataset, batch_size: int = 16, device=None):
     """evaluate_generic_objectness.py:180-279 without files, wandb or plots -> (average metrics, n_fallback, n_images)."""
@@ -247,7 +327,10 @@ def predict(processor: MaskCutProcessor, dataset, batch_size: int = 16, device=N
         items = [dataset[i] for i in range(i0, min(i0 + batch_size, len(dataset)))]
         images = torch.stack([it["original_image"] for it in items]).to(dev)
         gt = torch.stack([it["gt_binary_mask"] for it in items]).to(dev)
-        rows, nf = processor.process_batch(images, gt, [int(it["num_objects"]) for it in items])
+        rgb = None
+        if processor.refine != "none" and "original_image_rgb" in items[0]:
+            rgb = torch.stack([it["original_image_rgb"] for it in items]).to(dev)
+        rows, nf = processor.process_batch(images, gt, [int(it["num_objects"]) for it in items], rgb)
         n_fallback += nf
         for r in rows:  # the reference's running average, image by image
             n += 1

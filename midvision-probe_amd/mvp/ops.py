@@ -596,6 +596,53 @@ def ncut_partition(v, pass_mask, painted, union_mask, seed, Bimg, h, w, prev_mas
     _traced("lds", "ncut_partition", 0, float(Bimg * h * w), lambda: lib.call("mvp_ncut_partition", a))
 
 
+CRF_MODES = {"normalise": 0, "init": 1, "step": 2}  # MVP_CRF_NORMALISE / _INIT / _STEP
+
+
+def crf_filter_pairs(B: int, H: int, W: int, inv_var_xy: float) -> float:
+    """Pair evaluations of one mvp_crf_filter launch: the library's rule (csrc/densecrf.hip) that a 16 x 16 tile pair is skipped when its
+    closest pixels already give a weight <= 2^-40; every pair of a tile pair that is not skipped is evaluated, padding included."""
+    import math
+
+    ty, tx = (H + 15) // 16, (W + 15) // 16
+    cs = 0.5 * math.log2(math.e) * inv_var_xy
+    gap = lambda d: max(0, d * 16 - 15)  # noqa: E731
+    pairs = 0
+    for dy in range(ty):
+        for dx in range(tx):
+            if cs * (gap(dx) ** 2 + gap(dy) ** 2) >= 40.0:
+                continue
+            pairs += (ty - dy) * (1 if dy == 0 else 2) * (tx - dx) * (1 if dx == 0 else 2)
+    return float(B) * pairs * 256.0 * 256.0
+
+
+def crf_filter(rgb, out, B, F, H, W, inv_var_xy, inv_var_rgb, *, inp=None, in_stride=None, out_stride=None, active=None) -> None:
+    """out[b, f, i] = sum over all pixels j of image b of exp(-|dxy|^2 inv_var_xy / 2 - |drgb|^2 inv_var_rgb / 2) inp[b, f, j], rgb
+    [B, H, W, 3] uint8, inp / out [B, >= F, H W] fp32 (inp None: the all-ones field): mvp_crf_filter.  Traced work = pair evaluations."""
+    a = lib.CrfFilterArgs(lib.ptr(rgb), lib.ptr(inp), lib.ptr(active), lib.ptr(out), F * H * W if in_stride is None else in_stride,
+                          F * H * W if out_stride is None else out_stride, B, F, H, W, inv_var_xy, inv_var_rgb)
+    _traced("valu", "crf_filter bilateral" if inv_var_rgb > 0 else "crf_filter spatial", 0, crf_filter_pairs(B, H, W, inv_var_xy),
+            lambda: lib.call("mvp_crf_filter", a))
+
+
+def crf_update(mode: str, norm_g, norm_b, B, F, N, *, mask=None, ones_g=None, ones_b=None, filt_g=None, filt_b=None, q=None, x_g=None,
+               x_b=None, map_out=None, stride=None, w_g=0.0, w_b=0.0, active=None) -> None:
+    """The pointwise part of the dense CRF ("normalise": K·1 -> n in place; "init": Q^0 from the mask; "step": one mean-field update from
+    the filtered fields), with the next filter inputs n Q and optionally the MAP bytes: mvp_crf_update."""
+    a = lib.CrfUpdateArgs(lib.ptr(mask), lib.ptr(active), lib.ptr(norm_g), lib.ptr(norm_b), lib.ptr(ones_g), lib.ptr(ones_b), lib.ptr(filt_g),
+                          lib.ptr(filt_b), lib.ptr(q), lib.ptr(x_g), lib.ptr(x_b), lib.ptr(map_out), F * N if stride is None else stride, N, B, F,
+                          CRF_MODES[mode], w_g, w_b)
+    _traced("hbm", "crf_update " + mode, 0, float(B * N * (8 if mode == "normalise" else F * 29)), lambda: lib.call("mvp_crf_update", a))
+
+
+def mask_finish(map_in, ref, refined, B, F, H, W, *, kept=None, union_mask=None, stride=None, active=None) -> None:
+    """refined [B, F, H W] bytes = binary_fill_holes(map), zeroed where its IoU with ref is below 0.5; union_mask [B, H W] = the hole-filled
+    OR of the active passes: mvp_mask_finish (``active``: [B, F] bytes)."""
+    a = lib.MaskFinishArgs(lib.ptr(map_in), lib.ptr(ref), lib.ptr(active), lib.ptr(refined), lib.ptr(kept), lib.ptr(union_mask),
+                           F * H * W if stride is None else stride, B, F, H, W)
+    _traced("lds", "mask_finish", 0, float(B * F * H * W), lambda: lib.call("mvp_mask_finish", a))
+
+
 def dwconv7_ln(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out, B: int, H: int, W: int,
                Cdim: int, eps: float, *, ldx: Optional[int] = None, out_f32: Optional[torch.Tensor] = None, out_f16: bool = False) -> None:
     """Depthwise 7x7 (padding 3) + LayerNorm over the channels of the channels-last fp32 map ``x`` [B, H, W, ldx] -> ``out`` (a Pair, an
