@@ -99,6 +99,9 @@ typedef struct {
                                 Added within 8: mvp_crf_filter, mvp_crf_update and mvp_mask_finish (dense-CRF refinement of the MaskCut masks: exact
                                 all-pairs Gaussian filtering, mean-field update, hole filling / IoU rule / union); new exports with their own tagged
                                 argument structs, no existing struct changed.
+                                Added within 8: mvp_augment_stats, mvp_augment_apply and mvp_augment_partials_bytes (device-side training
+                                augmentation: fused ColorJitter + shared flip / rotate / resized crop + normalisation); new exports with their own
+                                tagged argument structs, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -1224,6 +1227,63 @@ struct mvp_grn_args {
 int64_t mvp_grn_workspace_bytes(int B, int HW, int C4);
 int mvp_grn_stats(const mvp_grn_args*, void* stream);
 int mvp_grn_apply(const mvp_grn_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Device-side training augmentation of an NYU / NAVI batch (added within ABI 8; new exports with their own tagged argument structs,
+ * no existing struct changed).  Replaces what the reference runs per sample on the host in get_nyu_transforms (evals/datasets/utils.py:160-218)
+ * and nyu.py:227-239: RandomApply([ColorJitter(0.2, 0.2, 0.2, 0.2)], p=0.8) on the image, then ONE geometric transform shared by image, depth and
+ * normals (HorizontalFlip, Rotate(limit=10), RandomResizedCrop, all nearest-neighbour), then Normalize(mean, std).  The random draws are
+ * made on the host (mvp/augment.py: sample_params); the kernels read them from a device table of MVP_AUGMENT_WORDS 32-bit words per image:
+ *   word 0       flags: bit 0 = colour jitter on, bit 1 = horizontal flip, bit 2 = rotate
+ *   word 1       order of the jitter operations: bits [2i, 2i+1] = operation at position i (0 brightness, 1 contrast, 2 saturation, 3 hue)
+ *   words 2..5   fp32 factors: brightness, contrast, saturation (each multiplies), hue shift in turns
+ *   words 6, 7   fp32 cos(theta), sin(theta) of the rotation
+ *   words 8..11  int32 crop box x0, y0, cw, ch in the (flipped, rotated) H x W image; the full image is (0, 0, W, H)
+ *   words 12..15 reserved, zero
+ * Output pixel (dy, dx) of the Ho x Wo result takes source pixel (yy, xx) of EVERY input plane, composed from the three integer maps
+ *   crop:    sx = x0 + (dx * cw) / Wo,  sy = y0 + (dy * ch) / Ho                      (integer division: nearest resize without half-pixel)
+ *   rotate:  u = sx - (W-1)/2, v = sy - (H-1)/2;  rx = floor((W-1)/2 + cos*u - sin*v + 0.5), ry = floor((H-1)/2 + sin*u + cos*v + 0.5) in fp32
+ *            (fused multiply-adds, the sin term first), indices outside the image reflected without repeating the edge (reflect-101)
+ *   flip:    xx = W-1-rx
+ * which is exactly flip, then rotate, then crop-and-resize applied one after the other.  The box is clamped into the image first, so no
+ * table content makes a read leave the inputs.  The jitter uses torchvision's float-tensor formulas on values in [0, 1] (uint8 / 255), in
+ * fp32; it is evaluated at the gathered pixels only, except that the contrast operation's mean m is the mean grey value
+ * 0.2989 r + 0.587 g + 0.114 b over the WHOLE source image as it stands when contrast is reached: mvp_augment_stats writes, per image,
+ * MVP_AUGMENT_PARTIALS fp64 partial sums of it (one per workgroup, fixed order inside; zero for images whose jitter is off), and
+ * mvp_augment_apply adds them in index order and divides by H * W.  No atomics: the same inputs give the same bits.
+ * H, W >= 4; H * W <= 2^29; Ho, Wo >= 1.  partials: 8-byte aligned, >= mvp_augment_partials_bytes(B) bytes, no initialisation needed.
+ * mvp_augment_apply with partials == NULL treats every image's jitter as off (the validation path: normalisation only).
+ * ---------------------------------------------------------------------------------- */
+#define MVP_AUGMENT_WORDS 16
+#define MVP_AUGMENT_PARTIALS 32
+typedef struct mvp_augment_stats_args mvp_augment_stats_args;
+struct mvp_augment_stats_args {
+  const void* image;                  /* uint8 [B, H, W, 3] (image_u8 = 1) or fp32 [B, 3, H, W] in [0, 1] (image_u8 = 0)                */
+  const int32_t* params;              /* [B, MVP_AUGMENT_WORDS] on the device                                                        */
+  double* partials;                   /* [B, MVP_AUGMENT_PARTIALS] out                                                               */
+  int64_t partials_bytes;
+  int B, H, W;
+  int image_u8;
+};
+typedef struct mvp_augment_apply_args mvp_augment_apply_args;
+struct mvp_augment_apply_args {
+  const void* image;                  /* as mvp_augment_stats_args.image                                                             */
+  const float* depth;                 /* [B, 1, H, W] fp32                                                                           */
+  const float* snorm;                 /* [B, 3, H, W] fp32, or NULL                                                                  */
+  const int32_t* params;              /* [B, MVP_AUGMENT_WORDS] on the device                                                        */
+  const double* partials;             /* out of mvp_augment_stats for the same image and params, or NULL (no jitter)                 */
+  float* out_image;                   /* [B, 3, Ho, Wo] fp32, (v - mean) / std                                                       */
+  float* out_depth;                   /* [B, 1, Ho, Wo]                                                                              */
+  float* out_snorm;                   /* [B, 3, Ho, Wo], NULL iff snorm is                                                           */
+  int64_t partials_bytes;
+  int B, H, W, Ho, Wo;
+  int image_u8;
+  float mean_r, mean_g, mean_b;       /* Normalize(mean, std) of get_nyu_transforms; (0, 0, 0) / (1, 1, 1) for image_mean "None"     */
+  float std_r, std_g, std_b;
+};
+int64_t mvp_augment_partials_bytes(int B);
+int mvp_augment_stats(const mvp_augment_stats_args*, void* stream);
+int mvp_augment_apply(const mvp_augment_apply_args*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,10 +18,11 @@ def _make_dataset(cfg, split, **kwargs):
     if "task" in node:
         raise NotImplementedError("TaskonomyDataset wrapping (builder.py:47-49) is outside the hot path")
     if "_target_" not in node:  # configs/dataset/synthetic.yaml style
-        from .synthetic import SyntheticNYU
+        from .synthetic import SyntheticNYU, SyntheticNYURaw
 
-        return SyntheticNYU(split=split, num_samples=node.get("num_samples", node.get("num_batches", 8) * node.get("batch_size", 16)),
-                            image_size=node.get("image_size", (480, 640)), max_depth=node.get("max_depth", 10.0), **kwargs)
+        cls = SyntheticNYURaw if node.get("raw") else SyntheticNYU  # raw: uint8 pixels for mvp.augment.DeviceAugment
+        return cls(split=split, num_samples=node.get("num_samples", node.get("num_batches", 8) * node.get("batch_size", 16)),
+                   image_size=node.get("image_size", (480, 640)), max_depth=node.get("max_depth", 10.0), **kwargs)
     return config.instantiate(node, split=split, **kwargs)
 
 

@@ -79,3 +79,27 @@ class SyntheticVOC(Dataset):
         std = torch.tensor(self.STD).view(3, 1, 1)
         return {"original_image": (rgb - mean) / std, "original_image_rgb": rgb, "gt_binary_mask": mask.float().unsqueeze(0),
                 "num_objects": num_objects}
+
+
+class SyntheticNYURaw(SyntheticNYU):
+    """SyntheticNYU as a file reader would hand its samples to the device-side augmentation (mvp.augment.DeviceAugment): "image" is
+    uint8 [H, W, 3], raw pixels that are neither jittered nor normalised; "depth", "snorm" and "segmentation" follow SyntheticNYU's
+    contract.  The image has structure — a smooth ramp per channel plus a few soft coloured blobs, on top of a little noise — so that
+    hue and saturation have colour to act on and two crops of one image can be told apart."""
+
+    def __getitem__(self, i: int):
+        out = super().__getitem__(i)
+        g = torch.Generator().manual_seed((self.seed * 4 + self._salt) * 1_000_003 + i + 55_000_000)
+        H, W = self.hw
+        ys = torch.linspace(0.0, 1.0, H).view(H, 1)
+        xs = torch.linspace(0.0, 1.0, W).view(1, W)
+        u = torch.rand(3, 4, generator=g)
+        # one ramp per channel: direction, offset and gain drawn per sample
+        rgb = torch.stack([(u[c, 0] * xs + u[c, 1] * ys) * 0.5 + 0.25 * u[c, 2] for c in range(3)])
+        for _ in range(4):
+            v = torch.rand(6, generator=g)
+            bump = torch.exp(-(((ys - v[0]) / (0.08 + 0.2 * v[2])) ** 2 + ((xs - v[1]) / (0.08 + 0.2 * v[2])) ** 2))
+            rgb = rgb + bump.unsqueeze(0) * (v[3:6].view(3, 1, 1) - 0.4)
+        rgb = rgb + 0.02 * torch.randn(3, H, W, generator=g)
+        out["image"] = (rgb.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).permute(1, 2, 0).contiguous()
+        return out

@@ -246,6 +246,16 @@ class MaskFinishArgs(Struct, c_name="mvp_mask_finish_args"):  # hole filling, Io
                 ("B", _i), ("F", _i), ("H", _i), ("W", _i)]
 
 
+class AugmentStatsArgs(Struct, c_name="mvp_augment_stats_args"):  # training augmentation: the contrast mean's partial sums (added within ABI 8)
+    _fields_ = [("image", _vp), ("params", _vp), ("partials", _vp), ("partials_bytes", _i64), ("B", _i), ("H", _i), ("W", _i), ("image_u8", _i)]
+
+
+class AugmentApplyArgs(Struct, c_name="mvp_augment_apply_args"):  # training augmentation: jitter + shared gather + normalise (added within ABI 8)
+    _fields_ = [("image", _vp), ("depth", _vp), ("snorm", _vp), ("params", _vp), ("partials", _vp), ("out_image", _vp), ("out_depth", _vp),
+                ("out_snorm", _vp), ("partials_bytes", _i64), ("B", _i), ("H", _i), ("W", _i), ("Ho", _i), ("Wo", _i), ("image_u8", _i),
+                ("mean_r", _f), ("mean_g", _f), ("mean_b", _f), ("std_r", _f), ("std_g", _f), ("std_b", _f)]
+
+
 class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -410,6 +420,9 @@ SYMBOLS = {
     "mvp_crf_filter": CrfFilterArgs,
     "mvp_crf_update": CrfUpdateArgs,
     "mvp_mask_finish": MaskFinishArgs,
+    "mvp_augment_partials_bytes": None,
+    "mvp_augment_stats": AugmentStatsArgs,
+    "mvp_augment_apply": AugmentApplyArgs,
 }
 
 # the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)
@@ -431,6 +444,7 @@ SIGNATURES = {
     "mvp_twoafc_workspace_bytes": (_i64, [_i, _i, _i]),
     "mvp_ncut_workspace_bytes": (_i64, [_i, _i]),
     "mvp_grn_workspace_bytes": (_i64, [_i, _i, _i]),
+    "mvp_augment_partials_bytes": (_i64, [_i]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -685,3 +685,58 @@ def grn_apply(h: torch.Tensor, N: torch.Tensor, gamma: torch.Tensor, beta: torch
     """gamma (h N) + beta + h -> ``out`` (a Pair, an IlvPair or None) and / or ``out_f32``: mvp_grn_apply."""
     a = _grn_args(h, B, HW, C4, N=N, gamma=gamma, beta=beta, out=out, out_f32=out_f32)
     _traced("hbm", "grn_apply", 0, float(B * HW * C4 * 8), lambda: lib.call("mvp_grn_apply", a))
+
+
+def augment_partials(B: int, device) -> torch.Tensor:
+    """The [B, MVP_AUGMENT_PARTIALS] fp64 buffer augment_stats writes and augment_apply reads (no initialisation needed)."""
+    return torch.empty(int(lib.load().mvp_augment_partials_bytes(B)) // 8, dtype=torch.float64, device=device).view(B, -1)
+
+
+def _augment_image(image: torch.Tensor):
+    """(B, H, W, image_u8) of a uint8 [B, H, W, 3] or fp32 [B, 3, H, W] image batch."""
+    if image.dtype == torch.uint8 and image.dim() == 4 and image.shape[3] == 3:
+        B, H, W, u8 = image.shape[0], image.shape[1], image.shape[2], 1
+    elif image.dtype == torch.float32 and image.dim() == 4 and image.shape[1] == 3:
+        B, H, W, u8 = image.shape[0], image.shape[2], image.shape[3], 0
+    else:
+        raise lib.MvpError(f"augment: image must be uint8 [B, H, W, 3] or float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
+    if not image.is_contiguous():
+        raise lib.MvpError("augment: image must be contiguous")
+    return B, H, W, u8
+
+
+def augment_stats(image: torch.Tensor, params: torch.Tensor, partials: torch.Tensor) -> None:
+    """Per-image partial sums of the grey value the contrast operation averages (include/mvp_hip.h: mvp_augment_stats)."""
+    B, H, W, u8 = _augment_image(image)
+    _chk(params, torch.int32, "params")
+    _chk(partials, torch.float64, "partials")
+    if params.numel() < B * 16:
+        raise lib.MvpError("augment: the parameter table is too small for the batch")
+    a = lib.AugmentStatsArgs(lib.ptr(image), lib.ptr(params), lib.ptr(partials), partials.numel() * 8, B, H, W, u8)
+    _traced("hbm", "augment_stats", 0, float(B * H * W * (3 if u8 else 12)), lambda: lib.call("mvp_augment_stats", a))
+
+
+def augment_apply(image, depth, snorm, params, partials, out_image, out_depth, out_snorm, mean, std) -> None:
+    """Jitter + shared flip / rotate / resized crop + normalisation into out_image [B, 3, Ho, Wo], out_depth [B, 1, Ho, Wo] and
+    out_snorm [B, 3, Ho, Wo] (snorm / out_snorm may both be None; partials None = no jitter): mvp_augment_apply."""
+    B, H, W, u8 = _augment_image(image)
+    _chk(params, torch.int32, "params")
+    for t, name, ch in ((depth, "depth", 1), (snorm, "snorm", 3)):
+        if t is not None:
+            _chk(t, torch.float32, name)
+            if tuple(t.shape) != (B, ch, H, W):
+                raise lib.MvpError(f"augment: {name} must be [B, {ch}, H, W] = {(B, ch, H, W)}, got {tuple(t.shape)}")
+    Ho, Wo = out_image.shape[-2:]
+    for t, name, ch in ((out_image, "out_image", 3), (out_depth, "out_depth", 1), (out_snorm, "out_snorm", 3)):
+        if t is not None:
+            _chk(t, torch.float32, name)
+            if tuple(t.shape) != (B, ch, Ho, Wo):
+                raise lib.MvpError(f"augment: {name} must be {(B, ch, Ho, Wo)}, got {tuple(t.shape)}")
+    if params.numel() < B * 16 or (partials is not None and partials.numel() * 8 < int(lib.load().mvp_augment_partials_bytes(B))):
+        raise lib.MvpError("augment: the parameter table or the partials buffer is too small for the batch")
+    a = lib.AugmentApplyArgs(lib.ptr(image), lib.ptr(depth), lib.ptr(snorm), lib.ptr(params), lib.ptr(partials), lib.ptr(out_image),
+                             lib.ptr(out_depth), lib.ptr(out_snorm), partials.numel() * 8 if partials is not None else 0,
+                             B, H, W, Ho, Wo, u8, mean[0], mean[1], mean[2], std[0], std[1], std[2])
+    planes = 4 + (3 if snorm is not None else 0)
+    work = float(B * H * W * (3 if u8 else 12) + B * H * W * 4 * (planes - 3) + B * Ho * Wo * 4 * planes)
+    _traced("hbm", "augment_apply", 0, work, lambda: lib.call("mvp_augment_apply", a))

@@ -55,10 +55,22 @@ def main(argv):
     ds = cfg["dataset"]
     loader = build_loader(dict(ds, batch_size=cfg["batch_size"]), "train", cfg["batch_size"], num_gpus=world, num_workers=cfg.get("num_workers", 2),
                           with_snorm=False)
+    train_batches, wrap_valid = loader, (lambda ld: ld)
+    if ds.get("augment_train") or ds.get("raw"):
+        # the reference's get_nyu_transforms(augment=True) on the device, between the H2D prefetcher and the frozen forward; raw loaders
+        # (uint8 pixels) are normalised there too, on the validation side with nothing else
+        from mvp.augment import DeviceAugment
+        from mvp.prefetch import DevicePrefetcher
+
+        aug = dict(image_mean=ds.get("image_mean", "imagenet"), seed=int(cfg["system"]["random_seed"]), rank=rank)
+        train_batches = DeviceAugment(DevicePrefetcher(loader, dev, keys=("image", "depth", "snorm")), augment=bool(ds.get("augment_train")),
+                                      rotateflip=bool(ds.get("rotateflip", False)), **aug)
+        if ds.get("raw"):
+            wrap_valid = lambda ld: DeviceAugment(DevicePrefetcher(ld, dev, keys=("image", "depth", "snorm", "segmentation")), augment=False, **aug)  # noqa: E731
     model = config.instantiate(cfg["backbone"]).to(dev)
     probe = config.instantiate(cfg["probe"], feat_dim=model.feat_dim, max_depth=ds["max_depth"]).to(dev)
     if "vit-mae" in model.checkpoint_name or "sam" in model.checkpoint_name:  # train_depth.py:613-617
-        model.resize_pos_embed(image_size=tuple(loader.dataset[0]["image"].shape[-2:]))
+        model.resize_pos_embed(image_size=tuple(ds["image_size"]) if ds.get("raw") else tuple(loader.dataset[0]["image"].shape[-2:]))
     opt = FlatAdamW([{"params": probe.parameters(), "lr": cfg["optimizer"]["probe_lr"]}], overlap_comm=world > 1)
     n_ep = cfg["optimizer"]["n_epochs"]
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda e: cosine_decay_linear_warmup(
@@ -74,7 +86,7 @@ def main(argv):
             raise SystemExit("is_eval=True needs ckpt_path=<.../ckpt.pth> (refusing to validate a randomly initialised probe)")
         checkpoint.load_checkpoint(loaded_ckpt, model, probe, load_model=False)
     else:
-        hist = train(model, probe, loader, opt, sched, n_ep, detach_model=True, loss_fn=DepthLoss(), rank=rank, world_size=world)
+        hist = train(model, probe, train_batches, opt, sched, n_ep, detach_model=True, loss_fn=DepthLoss(), rank=rank, world_size=world)
     opt.finish_pending()
     if rank == 0:
         model.eval(); probe.eval()
@@ -83,8 +95,8 @@ def main(argv):
         timestamp, exp_name, exp_info = results.experiment_info(cfg, model, probe, ds["name"], ds["name"])
         out = os.path.join(cfg["output_dir"], "depth_exps", exp_name.replace("$", ""))
         ckpt = loaded_ckpt if is_eval else os.path.join(out, "ckpt.pth")  # the CSV's ckpt_path column names what was scored
-        sa_loss, sa_g, sa_l = validate(model, probe, build_loader(vcfg, "valid", cfg["batch_size"], with_snorm=False), DepthLoss(), is_navi=is_navi)
-        si_loss, si_g, si_l = validate(model, probe, build_loader(vcfg, "valid", cfg["batch_size"], with_snorm=False), DepthLoss(),
+        sa_loss, sa_g, sa_l = validate(model, probe, wrap_valid(build_loader(vcfg, "valid", cfg["batch_size"], with_snorm=False)), DepthLoss(), is_navi=is_navi)
+        si_loss, si_g, si_l = validate(model, probe, wrap_valid(build_loader(vcfg, "valid", cfg["batch_size"], with_snorm=False)), DepthLoss(),
                                        scale_invariant=True, is_navi=is_navi)
         print(f"train loss/epoch {hist} | SA valid loss {sa_loss:.4f} d1 {sa_g['d1']:.4f} rmse {sa_g['rmse']:.4f} | SI loss {si_loss:.4f} rmse {si_g['rmse']:.4f}")
         titles, row = results.depth_result_row(timestamp, exp_info, sa_g, si_g, sa_l, si_l, ckpt, ds["name"])

@@ -36,6 +36,17 @@ def main(argv):
     hw, B = tuple(ds["image_size"]), cfg["batch_size"]
     loader = build_loader(dict(ds, batch_size=B), "train", B, num_gpus=world, num_workers=cfg.get("num_workers", 2))
     nb = len(loader)
+    augmented, wrap_valid = None, (lambda ld: ld)
+    if ds.get("augment_train") or ds.get("raw"):
+        # the reference's get_nyu_transforms(augment=True) on the device, between the H2D prefetcher and the frozen forward; raw loaders
+        # (uint8 pixels) are normalised there too, on the validation side with nothing else
+        from mvp.augment import DeviceAugment
+
+        aug = dict(image_mean=ds.get("image_mean", "imagenet"), seed=int(cfg["system"]["random_seed"]), rank=rank)
+        augmented = DeviceAugment(DevicePrefetcher(loader, dev, keys=("image", "depth", "snorm")), augment=bool(ds.get("augment_train")),
+                                  rotateflip=bool(ds.get("rotateflip", False)), **aug)
+        if ds.get("raw"):
+            wrap_valid = lambda ld: DeviceAugment(DevicePrefetcher(ld, dev, keys=("image", "depth", "snorm")), augment=False, **aug)  # noqa: E731
     model = config.instantiate(cfg["backbone"]).to(dev)
     probe = config.instantiate(cfg["probe"], feat_dim=model.feat_dim).to(dev)
     opt = FlatAdamW([{"params": probe.parameters(), "lr": cfg["optimizer"]["probe_lr"]}], overlap_comm=world > 1)
@@ -52,7 +63,10 @@ def main(argv):
         tot = 0.0
         if world > 1:
             loader.sampler.set_epoch(ep)
-        for batch, feats in pipelined_features(model, DevicePrefetcher(loader, dev), probe=probe):  # forward of the next batch already in flight
+        if augmented is not None:
+            augmented.set_epoch(ep)  # the epoch enters the draws' seed (and reaches the sampler again)
+        batches = augmented if augmented is not None else DevicePrefetcher(loader, dev)
+        for batch, feats in pipelined_features(model, batches, probe=probe):  # forward of the next batch already in flight
             target = batch["snorm"]
             mask = batch["depth"] > 0                               # train_snorm.py:95
             tot += train_snorm_step(model, probe, opt, sched, None, target, mask, feats=feats).item()
@@ -61,7 +75,7 @@ def main(argv):
     opt.finish_pending()
     if rank == 0:
         model.eval(); probe.eval()
-        b = next(iter(build_loader(dict(ds, num_batches=1, batch_size=B), "valid", B)))
+        b = next(iter(wrap_valid(build_loader(dict(ds, num_batches=1, batch_size=B), "valid", B))))
         with torch.no_grad():
             pred = MF.interpolate(probe(model(b["image"].to(dev))).contiguous(), size=hw, mode="bicubic")
         gm, _, _ = evaluate_surface_norm(pred, b["snorm"].to(dev), None, image_average=True, is_navi=True)
