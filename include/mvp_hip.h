@@ -102,6 +102,9 @@ typedef struct {
                                 Added within 8: mvp_augment_stats, mvp_augment_apply and mvp_augment_partials_bytes (device-side training
                                 augmentation: fused ColorJitter + shared flip / rotate / resized crop + normalisation); new exports with their own
                                 tagged argument structs, no existing struct changed.
+                                Added within 8: mvp_swiglu_fwd (the gate of DINOv2's SwiGLU MLP, silu(x1) * x2 between the w12 and w3 GEMMs of
+                                ViT-g/14, written as the zero-padded A operand pair of w3); a new export with its own tagged argument struct,
+                                no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -1284,6 +1287,36 @@ struct mvp_augment_apply_args {
 int64_t mvp_augment_partials_bytes(int B);
 int mvp_augment_stats(const mvp_augment_stats_args*, void* stream);
 int mvp_augment_apply(const mvp_augment_apply_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The gate of DINOv2's SwiGLU MLP (added within ABI 8; a new export with its own tagged argument struct, no existing struct changed).
+ * Replaces the middle of SwiGLUFFNFused.forward, which the reference runs inside torch.hub's dinov2_vitg14 (evals/models/dino.py:25-32,
+ * "vitg14"): x12 = w12(x); x1, x2 = x12.chunk(2, dim=-1); out = w3(F.silu(x1) * x2), hidden width H = (int(4C * 2 / 3) + 7) / 8 * 8
+ * (4096 at C = 1536).  The two Linear layers are GEMMs of this library; this is the pointwise step between them:
+ *   out[m, c] = silu(h12[m, c]) * h12[m, H + c],   silu(x) = x / (1 + exp2(-x log2 e))     (c < H)
+ *   out[m, c] = 0                                                                           (H <= c < ld_out, pair outputs only)
+ * in fp32 with one v_exp_f32 and one v_rcp_f32 per element, multiply-adds spelled out (no contraction): the same inputs give the same
+ * bits.  The exponent argument keeps the rounding error of x * log2 e as a first-order correction of the sigmoid (csrc/swiglu.hip).
+ * A gate below about -87 may return +-0 (the sigmoid is subnormal there and the reciprocal may flush it; from about -88.7 down exp2
+ * overflows and the reciprocal is 0); NaN propagates; an fp16 half saturates at +-65504 like
+ * every compensated pair of this library.  The pair halves are bit for bit what mvp_layernorm_fwd writes for the same fp32 value.
+ * The zero columns let the w3 GEMM run at K = ld_out (the tile kernels take K % 64, % 32 in bf16x3; H is a multiple of 8 only) against
+ * weights padded with zero columns.  M >= 1, H >= 8, H % 8 == 0, M * ld_out / 8 < 2^31, every pointer 16-byte aligned; anything else
+ * is MVP_EINVAL before any launch.  No output may alias h12.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_swiglu_args mvp_swiglu_args;
+struct mvp_swiglu_args {
+  const float* h12;                   /* [M, ld_in] fp32: gate in columns 0 .. H-1, value in H .. 2H-1 (mvp_gemm_args.out_f32 of w12)  */
+  mvp_bf16* out_hi; mvp_bf16* out_lo; /* [M, ld_out] pair as mvp_layernorm_args writes it; both NULL needs out_f32; lo may be NULL only
+                                         for MVP_PAIR_SEPARATE with out_f16 = 0 (the operand of a one-product bf16 GEMM)               */
+  float* out_f32;                     /* optional fp32 copy [M, H] (row stride H), or NULL                                           */
+  int M, H;
+  int ld_in;                          /* row stride of h12, elements: >= 2H, % 4 == 0                                                */
+  int ld_out;                         /* columns of a pair row: >= H, % 8 == 0 (% 32 for MVP_PAIR_A_ILV32, whose row stride is 2 ld_out) */
+  int out_layout;                     /* MVP_PAIR_SEPARATE or MVP_PAIR_A_ILV32, as mvp_layernorm_args.out_layout                     */
+  int out_f16;                        /* 1: the pair is the activation operand of MVP_PREC_F16X2, as mvp_layernorm_args.out_f16      */
+};
+int mvp_swiglu_fwd(const mvp_swiglu_args*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """evals.models.dino.DINO — drop-in for the reference wrapper (evals/models/dino.py:9-210),
-ViT-B/16 and DINOv2 (ViT-B/14, B/14 with registers, L/14) dense (multi-layer) feature extraction on the HIP kernels."""
+DINO ViT-B/16 and ViT-B/8 and DINOv2 (ViT-B/14, B/14 with registers, L/14, g/14) dense (multi-layer) feature extraction on the HIP kernels."""
 from __future__ import annotations
 
 import warnings
@@ -10,6 +10,9 @@ import torch.nn as nn
 from mvp import backbone as bb
 
 
+DINO_ARCH = {"vitb16": ("dino_vitbase16_pretrain", 16), "vitb8": ("dino_vitbase8_pretrain", 8)}  # model_name -> (torch.hub file, patch size); ViT-B both
+
+
 class DINO(bb.ViTBackbone):
     def __init__(self, dino_name="dino", model_name="vitb16", output="dense", layer=-1, return_multilayer=False, add_norm=False,
                  return_kqv=False, fixed_size=480, mode_selected="k", return_layers=None, return_cls=False,
@@ -17,10 +20,9 @@ class DINO(bb.ViTBackbone):
         super().__init__()
         feat_dims = {"vitb8": 768, "vitb16": 768, "vitb14": 768, "vitb14_reg": 768, "vitl14": 1024, "vitg14": 1536}
         v2 = dino_name == "dinov2"
-        if v2 and model_name == "vitg14":
-            raise NotImplementedError("dinov2 vitg14: its SwiGLU MLP (C = 1536) has no HIP path; vitb14, vitb14_reg and vitl14 do")
-        if not ((dino_name == "dino" and model_name == "vitb16") or (v2 and model_name in bb.DINOV2_ARCH)):
-            raise NotImplementedError("the HIP path covers DINO ViT-B/16 and DINOv2 ViT-B/14, B/14-reg, L/14 (configs/backbone/dino_b16.yaml, dinov2_*.yaml)")
+        if not ((dino_name == "dino" and model_name in DINO_ARCH) or (v2 and model_name in bb.DINOV2_ARCH)):
+            raise NotImplementedError("the HIP path covers DINO ViT-B/16, B/8 and DINOv2 ViT-B/14, B/14-reg, L/14, g/14 "
+                                      "(configs/backbone/dino_b16.yaml, dino_b8.yaml, dinov2_*.yaml)")
         if v2 and return_kqv:
             # the reference's extract_kqv calls self.vit.prepare_tokens (dino.py:104), which DINOv2's hub model does not have
             raise NotImplementedError("return_kqv with dinov2: the reference's extract_kqv has no DINOv2 path (prepare_tokens)")
@@ -34,17 +36,21 @@ class DINO(bb.ViTBackbone):
         # local checkpoint (MVP_CKPT_DIR/<checkpoint_name>.pth) or an explicit state dict, else seeded random init.
         sd = weights
         if sd is None:
-            hub = bb.DINOV2_HUB_NAMES[model_name] if v2 else "dino_vitbase16_pretrain"
+            hub = bb.DINOV2_HUB_NAMES[model_name] if v2 else DINO_ARCH[model_name][0]
             path = bb.find_checkpoint(self.checkpoint_name, hub)
             if path is not None:
                 sd = bb.load_checkpoint_file(path)
+            elif v2 and bb.DINOV2_FFN.get(model_name) == "swiglu":
+                # 4.4 GB of random weights in place of a missing file is never what was meant
+                raise NotImplementedError(f"dinov2 {model_name} (SwiGLU MLP, 1.1 B parameters): no local checkpoint and no weights=; "
+                                          "the seeded random-init fallback is not offered at this size")
             else:
                 warnings.warn(f"no local checkpoint for {self.checkpoint_name}: using seeded random init (seed={init_seed})")
                 if v2:
                     C, depth, R = bb.DINOV2_ARCH[model_name]
                     sd = bb.random_dinov2_state_dict(C, depth, R, seed=init_seed)
                 else:
-                    sd = bb.random_vit_state_dict(seed=init_seed)
+                    sd = bb.random_vit_state_dict(patch=DINO_ARCH[model_name][1], seed=init_seed)
         if v2:
             sd = bb.dinov2_hub_to_engine(sd)
         self.vit = bb.ViTParams(sd).eval()

@@ -83,14 +83,26 @@ DINOV2_ARCH = {  # model_name -> (embed_dim, depth, register tokens); heads = em
     "vitb14": (768, 12, 0),
     "vitb14_reg": (768, 12, 4),
     "vitl14": (1024, 24, 0),
+    "vitg14": (1536, 40, 0),
 }
-DINOV2_HUB_NAMES = {"vitb14": "dinov2_vitb14_pretrain", "vitb14_reg": "dinov2_vitb14_reg4_pretrain", "vitl14": "dinov2_vitl14_pretrain"}
+DINOV2_FFN = {"vitg14": "swiglu"}  # model_name -> the MLP of its blocks where it is not fc1 / GELU / fc2 ("mlp"): SwiGLUFFNFused, w3(silu(x1) * x2)
+DINOV2_HUB_NAMES = {"vitb14": "dinov2_vitb14_pretrain", "vitb14_reg": "dinov2_vitb14_reg4_pretrain", "vitl14": "dinov2_vitl14_pretrain",
+                    "vitg14": "dinov2_vitg14_pretrain"}
 
 
-def random_dinov2_state_dict(embed_dim=768, depth=12, registers=0, patch=14, pos_grid=37, seed=0, in_chans=3) -> Dict[str, torch.Tensor]:
+def swiglu_hidden(embed_dim: int, mlp_ratio: float = 4.0) -> int:
+    """Hidden width H of DINOv2's SwiGLUFFNFused: (int(hidden_features * 2 / 3) + 7) // 8 * 8 with hidden_features = int(C * mlp_ratio);
+    344 at C = 128, 512 at 192, 4096 at 1536."""
+    return (int(int(embed_dim * mlp_ratio) * 2 / 3) + 7) // 8 * 8
+
+
+def random_dinov2_state_dict(embed_dim=768, depth=12, registers=0, patch=14, pos_grid=37, seed=0, in_chans=3, ffn="mlp") -> Dict[str, torch.Tensor]:
     """Seeded random DINOv2 weights in the torch.hub key layout (used when no local checkpoint exists): the ViT statistics of
     random_vit_state_dict, a pos_grid x pos_grid pos-embed (518 / 14 = 37), random register tokens, LayerScale gammas drawn log-uniform
-    over [1e-6, 1] (trained DINOv2 models keep gammas from ~1e-5 to ~1), plus mask_token and the final norm (loaded, unused here)."""
+    over [1e-6, 1] (trained DINOv2 models keep gammas from ~1e-5 to ~1), plus mask_token and the final norm (loaded, unused here).
+    ``ffn``: 'mlp' (fc1 / fc2, hidden 4C) or 'swiglu' (ViT-g/14: ``mlp.w12`` [2H, C] and ``mlp.w3`` [C, H], H = swiglu_hidden(C))."""
+    if ffn not in ("mlp", "swiglu"):
+        raise ValueError(f"ffn {ffn!r}: 'mlp' or 'swiglu'")
     g = torch.Generator().manual_seed(seed)
 
     def tn(*shape, std=0.02):
@@ -116,8 +128,13 @@ def random_dinov2_state_dict(embed_dim=768, depth=12, registers=0, patch=14, pos
         sd[p + "attn.qkv.weight"], sd[p + "attn.qkv.bias"] = tn(3 * embed_dim, embed_dim), tn(3 * embed_dim)
         sd[p + "attn.proj.weight"], sd[p + "attn.proj.bias"] = tn(embed_dim, embed_dim), tn(embed_dim)
         sd[p + "ls1.gamma"] = gamma()
-        sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"] = tn(hid, embed_dim), tn(hid)
-        sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"] = tn(embed_dim, hid), tn(embed_dim)
+        if ffn == "swiglu":
+            glu = swiglu_hidden(embed_dim)
+            sd[p + "mlp.w12.weight"], sd[p + "mlp.w12.bias"] = tn(2 * glu, embed_dim), tn(2 * glu)
+            sd[p + "mlp.w3.weight"], sd[p + "mlp.w3.bias"] = tn(embed_dim, glu), tn(embed_dim)
+        else:
+            sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"] = tn(hid, embed_dim), tn(hid)
+            sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"] = tn(embed_dim, hid), tn(embed_dim)
         sd[p + "ls2.gamma"] = gamma()
     sd["norm.weight"], sd["norm.bias"] = torch.ones(embed_dim), torch.zeros(embed_dim)
     return sd
@@ -126,7 +143,7 @@ def random_dinov2_state_dict(embed_dim=768, depth=12, registers=0, patch=14, pos
 def dinov2_hub_to_engine(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """A DINOv2 torch.hub state dict -> the keys the engine reads: chunked blocks (``blocks.<chunk>.<i>.``, block_chunks > 0) are
     flattened to ``blocks.<i>.``; ``mask_token`` (masked pre-training only) and the final ``norm.*`` (not on the tap path,
-    dino.py:176-207) are dropped."""
+    dino.py:176-207) are dropped.  Every other key passes through under its own name, ViT-g/14's ``mlp.w12.*`` / ``mlp.w3.*`` included."""
     out = {}
     for k, v in sd.items():
         if k == "mask_token" or k.startswith("norm."):

@@ -256,6 +256,11 @@ class AugmentApplyArgs(Struct, c_name="mvp_augment_apply_args"):  # training aug
                 ("mean_r", _f), ("mean_g", _f), ("mean_b", _f), ("std_r", _f), ("std_g", _f), ("std_b", _f)]
 
 
+class SwigluArgs(Struct, c_name="mvp_swiglu_args"):  # DINOv2 ViT-g/14: silu(gate) * value -> the padded A operand of w3 (added within ABI 8)
+    _fields_ = [("h12", _vp), ("out_hi", _vp), ("out_lo", _vp), ("out_f32", _vp), ("M", _i), ("H", _i), ("ld_in", _i), ("ld_out", _i),
+                ("out_layout", _i), ("out_f16", _i)]
+
+
 class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -423,6 +428,7 @@ SYMBOLS = {
     "mvp_augment_partials_bytes": None,
     "mvp_augment_stats": AugmentStatsArgs,
     "mvp_augment_apply": AugmentApplyArgs,
+    "mvp_swiglu_fwd": SwigluArgs,
 }
 
 # the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)

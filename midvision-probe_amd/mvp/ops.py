@@ -687,6 +687,26 @@ def grn_apply(h: torch.Tensor, N: torch.Tensor, gamma: torch.Tensor, beta: torch
     _traced("hbm", "grn_apply", 0, float(B * HW * C4 * 8), lambda: lib.call("mvp_grn_apply", a))
 
 
+def swiglu(h12: torch.Tensor, out, M: int, H: int, *, ld_in: Optional[int] = None, ld_out: Optional[int] = None,
+           out_f32: Optional[torch.Tensor] = None, precision: int = PREC_BF16X3) -> None:
+    """silu(h12[:, :H]) * h12[:, H:2H] of the fp32 ``h12`` [M, ld_in] (``gemm(..., out_f32=...)`` of DINOv2's w12) -> ``out`` (a Pair, an
+    IlvPair or None) with ``ld_out`` >= H columns, the ones from H on zero, and / or ``out_f32`` [M, H]: mvp_swiglu_fwd.  ``precision``
+    PREC_F16X2: the pair is the activation operand of a two-product GEMM (``split_f16_comp``'s form), else a bf16 pair."""
+    ilv = isinstance(out, IlvPair)
+    if ilv:
+        ld_out = out.cols if ld_out is None else ld_out
+        out = (out.t, None)
+    elif out is None:
+        out = (None, None)
+    ld_in = 2 * H if ld_in is None else ld_in
+    ld_out = H if ld_out is None else ld_out
+    a = lib.SwigluArgs(lib.ptr(h12), lib.ptr(out[0]), lib.ptr(out[1]), lib.ptr(out_f32), M, H, ld_in, ld_out,
+                       lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE, 1 if precision == lib.PREC_F16X2 else 0)
+    # algorithmic HBM bytes: gate and value read once, the pair (or single bf16) and the fp32 copy written once
+    nb = M * H * (8 + (2 * (2 if (ilv or out[1] is not None) else 1) if out[0] is not None else 0) + (4 if out_f32 is not None else 0))
+    _traced("hbm", "swiglu_kernel", 0, float(nb), lambda: lib.call("mvp_swiglu_fwd", a))
+
+
 def augment_partials(B: int, device) -> torch.Tensor:
     """The [B, MVP_AUGMENT_PARTIALS] fp64 buffer augment_stats writes and augment_apply reads (no initialisation needed)."""
     return torch.empty(int(lib.load().mvp_augment_partials_bytes(B)) // 8, dtype=torch.float64, device=device).view(B, -1)

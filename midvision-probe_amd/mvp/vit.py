@@ -5,6 +5,7 @@ LayerNorm eps and which block outputs are tapped).
 DINOv2 (ViT-B/14, B/14 with registers, L/14) runs on the same engine: R register tokens follow the CLS row (n_prefix = 1 + R prefix
 rows per image, written by mvp_prefix_rows), LayerScale vectors (blocks.i.ls1.gamma / ls2.gamma) are applied in the proj / fc2 epilogues
 (mvp_gemm_scaled), and the 14x14 patches are gathered into zero-padded rows (mvp_patch_gather_ld) against zero-padded weights.
+ViT-g/14's SwiGLU MLP (blocks.i.mlp.w12 / mlp.w3) runs as the w12 GEMM into fp32, mvp_swiglu_fwd, and the w3 GEMM in fc2's place.
 
 BEiT v2 runs on it too: no position table, a learned relative-position bias per block expanded once into a dense [H, N, ld] array and
 added to the attention logits (mvp_attention_bias_fwd; ``rel_pos_grid``), and the reference wrapper's replay pass (``replay_after_norm``).
@@ -14,7 +15,8 @@ Data layout in HBM (per batch of B images, N = n_prefix + gh*gw tokens, n_prefix
   xn       bf16 pair [M, C]  LayerNorm output = A operand of the next GEMM
   qkv      bf16 pair [M, 3C] fused projection, read in place by the attention kernel
   ao       bf16 pair [M, C]  attention output (already in (B, N, H*64) order)
-  hmid     bf16 pair [M, 4C] fc1+GELU output
+  hmid     bf16 pair [M, hidden] fc1+GELU output (hidden = 4C; a SwiGLU model: silu(gate) * value, hidden = H padded to a multiple of 64)
+  h12      fp32  [M, 2H]     SwiGLU models only (DINOv2 ViT-g/14): the w12 projection, gate | value, read once by mvp_swiglu_fwd
   weights  bf16 pairs, torch Linear layout [N_out, K] (K contiguous) — split once at load.
 Everything is allocated once per (B, gh, gw) and reused: the frozen forward allocates only
 the returned NCHW maps.
@@ -236,6 +238,9 @@ class ViTEngine:
         DINOv2's register models), or 'resize_aa' (the same resample, applied whenever the table's grid-entry COUNT differs from
         gh * gw — the reference's resize_pos_embed, evals/models/utils.py:12-52 — with or without a CLS entry).
         act: the activation after fc1: 'gelu' (erf), 'quick_gelu' (x sigmoid(1.702 x): OpenAI CLIP) or 'gelu_tanh' (SigLIP).
+        A state dict with ``blocks.i.mlp.w12.weight`` [2H, C] / ``mlp.w3.weight`` [C, H] (DINOv2's SwiGLUFFNFused: ViT-g/14) makes a SwiGLU
+        engine whatever ``act`` says (``act_name`` = 'swiglu'): w12 into fp32 [M, 2H], mvp_swiglu_fwd into the A operand of w3 with H padded
+        to ``hidden`` = 64 * ceil(H / 64) zero columns (the GEMMs' K rule; ``w3`` is padded with zero columns once, here), w3 where fc2 runs.
         rope_freq: CroCo v2's RoPE<freq> (100.0 for the published models): Q and K of every block are rotated by the token's (y, x) grid
         position (mvp_rope2d_qkv, between the qkv GEMM — which then writes fp32 — and attention).  The state dict may then come without
         ``pos_embed`` (C is read from the patch-embedding weight and ``tokens`` adds no position residual).
@@ -306,23 +311,37 @@ class ViTEngine:
         self._sam_tables: List[Tuple[torch.Tensor, torch.Tensor]] = []  # distinct (rel_pos_h, rel_pos_w) on the CPU
         self._sam_rel: Dict[Tuple[int, int, int], Tuple[torch.Tensor, torch.Tensor]] = {}  # (table id, Kh, Kw) -> (Rh, Rw) on the device
         self._sam_win: Dict[Tuple[int, int, int, int], Tuple[torch.Tensor, torch.Tensor, int]] = {}  # (B, gh, gw, w) -> (part, unpart, windows)
+        self.swiglu = "blocks.0.mlp.w12.weight" in sd  # DINOv2's SwiGLUFFNFused (ViT-g/14)
+        if self.swiglu:
+            self.act_name, self.act = "swiglu", lib.ACT_NONE
+            self.swiglu_h = sd["blocks.0.mlp.w12.weight"].shape[0] // 2
+            self.hidden = -(-self.swiglu_h // 64) * 64
         self.blocks = []
         self._bias_tables: List[Tuple[torch.Tensor, torch.Tensor]] = []  # (table on the CPU, its dense [H, N, ld] bias on the device)
         for i in range(self.depth):
             p = f"blocks.{i}."
+            # the two MLP projections: fc1 / fc2, or a SwiGLU block's w12 / w3 in their places (w3 [C, H] zero padded to [C, hidden])
+            fc1, fc2 = ("mlp.w12", "mlp.w3") if self.swiglu else ("mlp.fc1", "mlp.fc2")
+            w = {"qkv_w": sd[p + "attn.qkv.weight"], "proj_w": sd[p + "attn.proj.weight"], "fc1_w": sd[p + fc1 + ".weight"], "fc2_w": sd[p + fc2 + ".weight"]}
+            if self.swiglu:
+                if tuple(w["fc1_w"].shape) != (2 * self.swiglu_h, self.C) or tuple(w["fc2_w"].shape) != (self.C, self.swiglu_h):
+                    raise lib.MvpError(f"block {i}: mlp.w12 / mlp.w3 of {tuple(w['fc1_w'].shape)} / {tuple(w['fc2_w'].shape)}: "
+                                       f"[2H, C] / [C, H] with H = {self.swiglu_h}, C = {self.C} expected")
+                if self.hidden != self.swiglu_h:
+                    w["fc2_w"] = F.pad(w["fc2_w"], (0, self.hidden - self.swiglu_h)).contiguous()
             blk = dict(
                 n1w=sd[p + "norm1.weight"], n1b=sd[p + "norm1.bias"],
-                qkv_w=ops.split_bf16(sd[p + "attn.qkv.weight"], self.precision),
+                qkv_w=ops.split_bf16(w["qkv_w"], self.precision),
                 qkv_b=sd.get(p + "attn.qkv.bias"),
-                proj_w=ops.split_bf16(sd[p + "attn.proj.weight"], self.precision), proj_b=sd[p + "attn.proj.bias"],
+                proj_w=ops.split_bf16(w["proj_w"], self.precision), proj_b=sd[p + "attn.proj.bias"],
                 n2w=sd[p + "norm2.weight"], n2b=sd[p + "norm2.bias"],
-                fc1_w=ops.split_bf16(sd[p + "mlp.fc1.weight"], self.precision), fc1_b=sd[p + "mlp.fc1.bias"],
-                fc2_w=ops.split_bf16(sd[p + "mlp.fc2.weight"], self.precision), fc2_b=sd[p + "mlp.fc2.bias"],
+                fc1_w=ops.split_bf16(w["fc1_w"], self.precision), fc1_b=sd[p + fc1 + ".bias"],
+                fc2_w=ops.split_bf16(w["fc2_w"], self.precision), fc2_b=sd[p + fc2 + ".bias"],
                 ls1=sd.get(p + "ls1.gamma"), ls2=sd.get(p + "ls2.gamma"),  # LayerScale (DINOv2) or None
             )
             if self.f16x2:  # the weight operands of the two-product GEMMs (ops.f16x2_weight: compensated fp16 pairs)
                 for n in ("qkv_w", "proj_w", "fc1_w", "fc2_w"):
-                    blk[n] = ops.f16x2_weight(sd[p + {"qkv_w": "attn.qkv.weight", "proj_w": "attn.proj.weight", "fc1_w": "mlp.fc1.weight", "fc2_w": "mlp.fc2.weight"}[n]])
+                    blk[n] = ops.f16x2_weight(w[n])
             if self.precision == PREC_BF16X3:  # hi|lo-interleaved copies of the frozen weights for the large-M GEMM kernel (mvp.ops.interleave_pair)
                 for n in ("qkv_w", "proj_w", "fc1_w", "fc2_w"):
                     blk[n + "_ilv"] = ops.interleave_pair(blk[n])
@@ -340,7 +359,9 @@ class ViTEngine:
             self.blocks.append(blk)
         self.fc_norm = (sd["fc_norm.weight"], sd["fc_norm.bias"]) if "fc_norm.weight" in sd else None  # BEiT's final norm (replay_after_norm)
         self._zero_c = torch.zeros(self.C, dtype=torch.float32, device=self.device) if self.pos_embed is None and self.has_cls else None
-        self.hidden = self.blocks[0]["fc1_b"].numel()
+        if not self.swiglu:
+            self.hidden = self.blocks[0]["fc1_b"].numel()
+        self.fc1_out = 2 * self.swiglu_h if self.swiglu else self.hidden  # columns the first MLP GEMM writes
         self._buffers = EngineBuffers()  # everything a forward reuses, per pipeline slot (mvp/buffers.py)
         self._pos: Dict[Tuple[int, int], torch.Tensor] = {}
         self._rope: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}  # (gh, gw) -> cos / sin tables [max(gh, gw), 32] (rope_for)
@@ -376,7 +397,7 @@ class ViTEngine:
                 for w in {b["window"] for b in self.blocks}:
                     Bp, Np, K = (B * -(-gh // w) * -(-gw // w), w * w, 2 * w) if w else (B, N, gh + gw)
                     Mp, nrel, windowed = max(Mp, Bp * Np), max(nrel, Bp * self.heads * Np * (-(-K // 4) * 4)), windowed or w > 0
-            shapes = [(M, 3 * C, C), (M, C, C), (M, self.hidden, C), (M, C, self.hidden)] + ([(Mp, 3 * C, C)] if windowed else [])
+            shapes = [(M, 3 * C, C), (M, C, C), (M, self.fc1_out, C), (M, C, self.hidden)] + ([(Mp, 3 * C, C)] if windowed else [])
             ilv = (pr == PREC_BF16X3 and os.environ.get("MVP_ILV", "1") != "0" and C % 32 == 0 and self.hidden % 32 == 0 and
                    all(ops.gemm_tile(m, n, k, gp, 1, pipeline.tile_policy()).startswith("pp ") for m, n, k in shapes))
             a_pair = lambda rows, cols: ops.IlvPair(rows, cols, dev) if ilv else ops.empty_pair((rows, cols), pr, dev)
@@ -389,8 +410,11 @@ class ViTEngine:
                            qkv=ops.empty_pair((Mp, 3 * C), pr, dev))
                 if windowed:  # LayerNorm 1's output and the attention output in window order (A operands like xn and ao)
                     sam.update(xw=a_pair(Mp, C), aow=a_pair(Mp, C))
+            # SwiGLU engines only: the fp32 w12 projection (gate | value) that mvp_swiglu_fwd reads
+            glu = dict(h12=torch.empty(M, self.fc1_out, dtype=torch.float32, device=dev)) if self.swiglu else {}
             return dict(
                 **rope,
+                **glu,
                 xfull=xfull, headroom=headroom, x=xfull[headroom * N:],
                 xn=a_pair(M, C),
                 qkv=sam["qkv"] if self.sam else ops.empty_pair((M, 3 * C), pr, dev),
@@ -618,10 +642,15 @@ class ViTEngine:
         ops.layernorm(x, blk["n2w"], blk["n2b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
         if chk:
             self._check_f16_range(f"block {i}: LayerNorm 2 output", ws["xn"], M)
-        ops.gemm(ws["xn"], blk["fc1_w"], M, self.hidden, C, bias=blk["fc1_b"], out=ws["hmid"], act=self.act, precision=gp, w_ilv=blk.get("fc1_w_ilv"),
-                 f16_col0=-1 if f2 else 0)
+        if self.swiglu:  # w12 as fp32 [M, 2H], then silu(gate) * value into the A operand of w3 (columns H .. hidden-1 zero)
+            ops.gemm(ws["xn"], blk["fc1_w"], M, self.fc1_out, C, bias=blk["fc1_b"], out_f32=ws["h12"], precision=gp, w_ilv=blk.get("fc1_w_ilv"))
+            ops.swiglu(ws["h12"], ws["hmid"], M, self.swiglu_h, ld_out=self.hidden, precision=gp)
+        else:
+            ops.gemm(ws["xn"], blk["fc1_w"], M, self.hidden, C, bias=blk["fc1_b"], out=ws["hmid"], act=self.act, precision=gp, w_ilv=blk.get("fc1_w_ilv"),
+                     f16_col0=-1 if f2 else 0)
         if chk:
-            self._check_f16_range(f"block {i}: {self.act_name}(fc1) output" if self.act_name != "gelu" else f"block {i}: GELU(fc1) output", ws["hmid"], M)
+            what = {"gelu": "GELU(fc1) output", "swiglu": "SwiGLU gate output silu(x1) * x2"}.get(self.act_name, f"{self.act_name}(fc1) output")
+            self._check_f16_range(f"block {i}: {what}", ws["hmid"], M)
         ops.gemm(ws["hmid"], blk["fc2_w"], M, C, self.hidden, bias=blk["fc2_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("fc2_w_ilv"),
                  col_scale=blk["ls2"])
 
