@@ -34,6 +34,11 @@ round), 7 batches are 261 (two rounds).  A forward may therefore cover a SPAN of
 cut batch and completes it in the next span's forward (ViTEngine.forward_taps, ``Span``): the tap BN still sees exactly one batch's
 16 images, so every batch still gets the bits it would get alone.  The carry (images of the cut batch already done) cycles through
 B / gcd(T, B) values; one graph per (slot, carry) pattern is captured at the pipeline's first submit.
+
+Structure.  ``_plan`` derives the shape of a pipeline (slots, streams, batches per group, images per span) from what its constructor was
+asked for, what the backbone can do and one batch shape, without a device; ``FeaturePipeline._apply`` is the one place that takes it
+over (first submit, ``rebind``).  ``_Feeder`` cuts a stream of batches into the forwards of that plan for ``pipelined_features``.
+``_LAUNCH`` is the one record of the forward being enqueued that the code below the pipeline reads (ops, buffers, the engines).
 """
 from __future__ import annotations
 
@@ -52,10 +57,14 @@ import torch
 # and a validation pass — never see each other's rows)
 Span = collections.namedtuple("Span", "batch carry stream", defaults=(0,))
 
-_SLOT = 0  # slot of the forward being enqueued (host state; kernels are enqueued by one host thread)
-_GROUPS = 1  # batches stacked into the forward being enqueued
-_PIPELINED = False
-_SHARED = False  # >= 3 kernel chains side by side: the GEMMs pick the tiles meant for a shared chip (mvp_hip.h, MVP_TILES_SHARED)
+# The forward being enqueued (host state; kernels are enqueued by one host thread):
+#   slot       the buffer set it owns
+#   groups     batches stacked into it, or the ``Span`` it covers
+#   pipelined  it runs on a pipeline side stream
+#   shared     >= 3 kernel chains side by side: the GEMMs pick the tiles meant for a shared chip (mvp_hip.h, MVP_TILES_SHARED)
+#   deferred   (batch of the group, update) registered by it, applied by the consumer in batch order
+_Launch = collections.namedtuple("_Launch", "slot groups pipelined shared deferred")
+_LAUNCH = _Launch(0, 1, False, False, [])
 SHARED_TILES_FROM = 3
 MAX_STREAMS = 3  # side streams = kernel chains running side by side; more than 3 measured slower (4: -14 %)
 
@@ -65,18 +74,18 @@ _NAMESPACES = itertools.count(1)  # one per FeaturePipeline: its slots' buffers 
 
 def current_slot():
     """Key of the buffer set the forward being enqueued owns: 0 outside a pipeline, (pipeline namespace, slot index) inside."""
-    return _SLOT
+    return _LAUNCH.slot
 
 
 def current_groups():
     """Number of equal batches stacked along dim 0 of the forward being enqueued (1 outside a grouped pipeline forward), or the
     ``Span`` the forward covers."""
-    return _GROUPS
+    return _LAUNCH.groups
 
 
 def pipelined() -> bool:
     """True while a forward is being enqueued on a pipeline side stream."""
-    return _PIPELINED
+    return _LAUNCH.pipelined
 
 
 class GroupedFeatures(list):
@@ -87,18 +96,22 @@ class GroupedFeatures(list):
 def tile_policy() -> int:
     """mvp_gemm_args.tile_policy of a GEMM launched now: 1 (MVP_TILES_SHARED) inside a forward of a pipeline that runs three kernel
     chains side by side, else 0 (MVP_TILES_ALONE)."""
-    return 1 if _SHARED else 0
+    return 1 if _LAUNCH.shared else 0
 
 
 @contextlib.contextmanager
-def _slot(i: int, chains: int = 2, groups: int = 1):
-    global _SLOT, _PIPELINED, _SHARED, _GROUPS
-    prev = (_SLOT, _PIPELINED, _SHARED, _GROUPS)
-    _SLOT, _PIPELINED, _SHARED, _GROUPS = i, True, chains >= SHARED_TILES_FROM, groups
+def _launch(record: _Launch):
+    global _LAUNCH
+    prev, _LAUNCH = _LAUNCH, record
     try:
         yield
     finally:
-        _SLOT, _PIPELINED, _SHARED, _GROUPS = prev
+        _LAUNCH = prev
+
+
+def _slot(i: int, chains: int = 2, groups: int = 1):
+    """The block enqueues one pipelined forward on slot ``i`` (it starts with no deferred update of its own)."""
+    return _launch(_Launch(i, groups, True, chains >= SHARED_TILES_FROM, []))
 
 
 def publish() -> None:
@@ -109,20 +122,17 @@ def publish() -> None:
         torch.cuda.synchronize()
 
 
-_DEFERRED = []  # (batch of the group, update) registered by the forward being enqueued, applied by the consumer in batch order
-
-
 def defer(fn, group: int = 0) -> None:
     """Register an update of state shared by all forwards (the tap-BN running statistics and step counter: the only state a frozen
     forward mutates).  A pipelined forward must not apply it itself — forwards on different streams finish in any order — so
     ``FeaturePipeline.next()`` runs it on the trainer's stream when the batch is handed over: batch order, no cross-stream event.
     ``group``: which batch of a grouped forward the update belongs to."""
-    _DEFERRED.append((group, fn))
+    _LAUNCH.deferred.append((group, fn))
 
 
 def _take_deferred():
-    global _DEFERRED
-    out, _DEFERRED = _DEFERRED, []
+    out = _LAUNCH.deferred[:]
+    del _LAUNCH.deferred[:]  # (emptied in place: a ``shared_tiles`` block shares the list with the record around it)
     return out
 
 
@@ -140,13 +150,8 @@ def freeze_gc() -> None:
 def shared_tiles(on: bool = True):
     """Force the GEMM tile policy of launches made inside the block (measurement: the shared-chip tiles on a serial chain, so that a
     profiler sees the kernels of a pipelined run one at a time)."""
-    global _SHARED
-    prev = _SHARED
-    _SHARED = bool(on)
-    try:
+    with _launch(_LAUNCH._replace(shared=bool(on))):
         yield
-    finally:
-        _SHARED = prev
 
 
 def default_depth(probe=None, group: int = 1) -> int:
@@ -185,8 +190,8 @@ MAX_GROUP = 8
 
 
 def default_group(model, images: torch.Tensor, depth: int) -> int:
-    """Batches per grouped forward for batches shaped like ``images``.  MVP_PIPELINE_GROUP wins when set.  1 when the pipeline runs
-    inline (depth 1) or the backbone cannot group; else as many batches as bring one forward to about GROUP_ROWS token rows."""
+    """Batches per grouped forward for batches shaped like ``images`` (a batch or its shape).  MVP_PIPELINE_GROUP wins when set.  1 when
+    the pipeline runs inline (depth 1) or the backbone cannot group; else as many batches as bring one forward to about GROUP_ROWS token rows."""
     env = os.environ.get("MVP_PIPELINE_GROUP")
     ok = getattr(model, "supports_grouping", None)
     if depth <= 1 or ok is None or not ok():
@@ -194,7 +199,8 @@ def default_group(model, images: torch.Tensor, depth: int) -> int:
     if env is not None:
         return max(1, min(MAX_GROUP, int(env)))
     P = int(getattr(model, "patch_size", 16))
-    B, H, W = images.shape[0], images.shape[-2], images.shape[-1]
+    shape = getattr(images, "shape", images)
+    B, H, W = shape[0], shape[-2], shape[-1]
     rows = B * rows_per_image(H, W, P, int(getattr(model, "n_prefix", 1)))
     return max(1, min(MAX_GROUP, int(round(GROUP_ROWS / rows))))
 
@@ -203,14 +209,16 @@ MAX_SPAN_PATTERNS = 16  # (slot, carry) patterns whose graphs are captured up fr
 
 
 def default_span(model, images: torch.Tensor, depth: int, group: int) -> int:
-    """IMAGES per forward when forwards may end in the middle of a batch (0: whole batches only).  MVP_PIPELINE_SPAN wins when set.
+    """IMAGES per forward when forwards may end in the middle of a batch (0: whole batches only), for batches shaped like ``images`` (a
+    batch or its shape).  MVP_PIPELINE_SPAN wins when set.
     As many images as keep the narrowest GEMM of a block (N = C columns: ceil(C / 256) column tiles of the 256x256 kernel) within
     one round of the device's CUs (256 on MI355X; mvp_info().cu_count), rounded down to a multiple of B / 8 (few carry patterns); 0 when that is a whole number of batches anyway
     (then ``group`` covers it), less than one batch, the pipeline is not the two-slot one, or a single batch already fills a forward
     (``group`` 1, e.g. B = 16 at 480x640: 18 images per forward on one stream measured 1293 img/s against 1349 for single batches on
     three streams, whose chains fill each other's partial rounds; at 224^2, B = 16 / 64: 8967 / 9203 against 8514 / 8191)."""
     env = os.environ.get("MVP_PIPELINE_SPAN")
-    B = images.shape[0]
+    shape = getattr(images, "shape", images)
+    B = shape[0]
     ok = getattr(model, "supports_grouping", None)
     if depth != 2 or ok is None or not ok() or (env is not None and int(env) <= 0):
         return 0
@@ -224,8 +232,7 @@ def default_span(model, images: torch.Tensor, depth: int, group: int) -> int:
         if C <= 0:
             return 0
         P = int(getattr(model, "patch_size", 16))
-        H, W = images.shape[-2], images.shape[-1]
-        rows = rows_per_image(H, W, P, int(getattr(eng, "n_prefix", 1)))
+        rows = rows_per_image(shape[-2], shape[-1], P, int(getattr(eng, "n_prefix", 1)))
         unit = max(1, B // 8)
         T = min(((_cu_count() // (-(-C // 256))) * 256) // rows, MAX_GROUP * B) // unit * unit
     return T if (T > B and T % B) else 0
@@ -270,6 +277,59 @@ def _multi_rank() -> bool:
     return bool(dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
 
 
+# what a FeaturePipeline was asked for (its constructor's arguments; None = not given) ...
+_Request = collections.namedtuple("_Request", "depth group span streams ungrouped_depth")
+# ... and the shape it takes: forwards submitted ahead (= buffer slots), side streams, batches per full group, images per span forward
+# and per batch of a span (0, 0: whole batches only)
+_Plan = collections.namedtuple("_Plan", "depth chains group span span_batch")
+
+
+def _plan(req: _Request, model, shape=None) -> _Plan:
+    """The shape of a pipeline over ``model`` for batches of ``shape`` (None: before the first batch is known — ``group`` is still
+    None when it was left to ``default_group``).  Reads the environment as ``default_depth`` / ``default_group`` / ``default_span``
+    do, and MVP_PIPELINE_STREAMS; touches no device."""
+    depth = default_depth() if req.depth is None else int(req.depth)
+    if not getattr(model, "supports_pipelining", False):
+        depth = 1
+    # ``depth`` forwards are submitted ahead (one buffer slot each); they run on ``streams`` side streams = kernel chains side by side
+    streams = req.streams if req.streams is not None else os.environ.get("MVP_PIPELINE_STREAMS")
+    streams_given = streams is not None
+    streams = int(streams) if streams_given else MAX_STREAMS
+    chains = max(1, min(depth, streams))
+    group = 1 if depth == 1 else (None if req.group is None else max(1, int(req.group)))
+    if shape is None:
+        return _Plan(depth, chains, group, 0, 0)
+    auto = group is None
+    depth_free = req.depth is None and os.environ.get("MVP_INFLIGHT") is None
+    B = shape[0]
+    if auto:
+        group = default_group(model, shape, depth)
+    # images per span forward (module docstring, "Spans"): None = default_span when ``group`` is chosen automatically, else off
+    span = 0
+    if depth > 1 and (depth == 2 or depth_free) and not (streams_given and streams != 1):
+        if req.span is not None:
+            span = int(req.span) if (int(req.span) > B and int(req.span) % B) else 0
+        elif auto:
+            span = default_span(model, shape, 2, group)
+    if span:
+        # span forwards: two slots, ONE side stream (it orders the carry store between consecutive forwards)
+        return _Plan(2, 1, max(group, -(-span // B)), span, B)
+    if auto and group > 1:
+        if depth_free:
+            # grouped forwards: two slots (one group being consumed, the next one's forward running); see default_depth
+            depth = 2
+        # ... on ONE side stream unless asked otherwise: a grouped forward's GEMMs fill the chip by themselves (one 256x256 tile per
+        # CU), a second forward chain beside them adds nothing (measured, B = 16, 6 batches per forward, img/s at 20 / 60 steps:
+        # one stream 8357 / 8706, two 8326 / 8714), and one chain keeps every per-kernel measurement in the regime of the timed run
+        chains = max(1, min(depth, streams if streams_given else 1))
+    elif auto and depth_free and req.ungrouped_depth is not None and req.ungrouped_depth < depth:
+        # depth to fall to when ``depth`` is None and the forwards turn out to be single batches (``default_depth(probe)``: a DPT probe
+        # step gains from grouped forwards beside it, 762 -> 802 img/s, but loses to single-batch ones, 739-748 -> 699-723)
+        depth = max(1, int(req.ungrouped_depth))
+        chains = max(1, min(depth, chains))
+    return _Plan(depth, chains, group, 0, 0)
+
+
 class FeaturePipeline:
     """``submit(images)`` enqueues ``model(images)`` on a side stream; ``next()`` returns the oldest submitted features on the
     caller's current stream (event wait, no host sync) after applying the forward's deferred state updates.  ``depth`` = forwards
@@ -293,33 +353,15 @@ class FeaturePipeline:
         The reference's loop syncs every step (``loss.item()``, train_depth.py:143); a loop that never syncs would otherwise queue
         hundreds of launches (and keep their argument buffers alive).  Throughput-neutral on MI355X (tools/micro/pipeline_probe.py,
         B=16, 300 steps, 2 in flight: 6526 img/s unbounded, 6565 with 8, 6584 with 3)."""
-        self._depth_arg = depth
-        depth = default_depth() if depth is None else int(depth)
-        if depth < 1:
+        if depth is not None and int(depth) < 1:
             raise ValueError("depth must be >= 1")
-        if not getattr(model, "supports_pipelining", False):
-            depth = 1
-        self.model, self.depth = model, depth
-        self.group = None if group is None else max(1, int(group))  # resolved at the first submit (needs the batch shape)
-        self._group_arg, self._resolved_for = self.group, None
-        if self.depth == 1:
-            self.group = 1
-        # images per span forward (module docstring, "Spans"): None = default_span when ``group`` is chosen automatically, else off
+        self.model = model
+        self._request = _Request(depth, group, span, streams, ungrouped_depth)
+        self._resolved_for = None  # (shape, dtype) of the batches the plan was made for: at the first submit (it needs the batch shape)
         self._ns = next(_NAMESPACES)
         self._lent = False  # pipelined_features: this (cached) pipeline is driving a loop right now
-        self._span_arg = span
-        # depth to fall to when ``depth`` is None and the forwards turn out to be single batches (``default_depth(probe)``: a DPT probe
-        # step gains from grouped forwards beside it, 762 -> 802 img/s, but loses to single-batch ones, 739-748 -> 699-723)
-        self._ungrouped_depth = ungrouped_depth
-        self.span, self.span_batch, self._span_resolved = 0, 0, False
-        # (stream priorities do not help: the device offers only (0, -1), and high-priority side streams measured the same)
-        # ``depth`` forwards are submitted ahead (one buffer slot each); they run on ``streams`` side streams = kernel chains side by side
-        self._streams_given = streams is not None or os.environ.get("MVP_PIPELINE_STREAMS") is not None
-        if streams is None:
-            streams = int(os.environ.get("MVP_PIPELINE_STREAMS", str(MAX_STREAMS)))
-        self._streams_arg = int(streams)
-        self.chains = max(1, min(depth, int(streams)))
-        self.streams = [torch.cuda.Stream() for _ in range(self.chains)] if depth > 1 else []
+        self.streams = []
+        self._apply(_plan(self._request, model))
         self._queue = collections.deque()  # one entry per BATCH: (features, completion event of its forward, deferred updates)
         self._open = collections.deque()   # per forward in flight: [batches of it not yet handed over, its slot]
         self._n = 0
@@ -334,7 +376,7 @@ class FeaturePipeline:
             # step, against the ~115 the probe step itself makes), so the eager default costs multi-rank jobs little.
             env = os.environ.get("MVP_PIPELINE_GRAPHS")
             graphs = (env != "0") if env is not None else not _multi_rank()
-        self.graphs = bool(graphs) and depth > 1 and bool(getattr(model, "graph_safe", False))
+        self.graphs = bool(graphs) and self.depth > 1 and bool(getattr(model, "graph_safe", False))
         self._warned_eager_span = False
         self.throttle_wait_s = 0.0  # wall time the host has spent waiting in the ``run_ahead`` throttle (not work: the device was behind)
         self._graphs = {}  # (slot, shape, dtype, training, engine id, group) -> dict(calls, graph, static_in, feats, deferred)
@@ -351,41 +393,18 @@ class FeaturePipeline:
 
     def resolve_group(self, images: torch.Tensor) -> int:
         """Fix the shape of the forwards at the first submit (needs the batch shape): batches per group, images per span, slots, streams."""
-        if self._span_resolved:
-            return self.group
-        self._span_resolved = True
-        self._resolved_for = (tuple(images.shape), images.dtype)
-        auto = self.group is None
-        depth_free = self._depth_arg is None and os.environ.get("MVP_INFLIGHT") is None
-        B = images.shape[0]
-        if auto:
-            self.group = default_group(self.model, images, self.depth)
-        span = 0
-        if self.depth > 1 and (self.depth == 2 or depth_free) and not (self._streams_given and self._streams_arg != 1):
-            if self._span_arg is not None:
-                span = int(self._span_arg) if (int(self._span_arg) > B and int(self._span_arg) % B) else 0
-            elif auto:
-                span = default_span(self.model, images, 2, self.group)
-        if span:
-            # span forwards: two slots, ONE side stream (it orders the carry store between consecutive forwards)
-            self.span, self.span_batch = span, B
-            self.depth, self.chains = 2, 1
-            self.streams = self.streams[:1] if self.streams else [torch.cuda.Stream()]
-            self.group = max(self.group, -(-span // B))
-        elif auto and self.group > 1:
-            if depth_free:
-                # grouped forwards: two slots (one group being consumed, the next one's forward running); see default_depth
-                self.depth = 2
-            # ... on ONE side stream unless asked otherwise: a grouped forward's GEMMs fill the chip by themselves (one 256x256 tile per
-            # CU), a second forward chain beside them adds nothing (measured, B = 16, 6 batches per forward, img/s at 20 / 60 steps:
-            # one stream 8357 / 8706, two 8326 / 8714), and one chain keeps every per-kernel measurement in the regime of the timed run
-            self.chains = max(1, min(self.depth, self._streams_arg if self._streams_given else 1))
-            self.streams = self.streams[:self.chains]
-        elif auto and depth_free and self._ungrouped_depth is not None and self._ungrouped_depth < self.depth:
-            self.depth = max(1, int(self._ungrouped_depth))
-            self.chains = max(1, min(self.depth, self.chains))
-            self.streams = self.streams[:self.chains] if self.depth > 1 else []
+        if self._resolved_for is None:
+            self._resolved_for = (tuple(images.shape), images.dtype)
+            self._apply(_plan(self._request, self.model, tuple(images.shape)))
         return self.group
+
+    def _apply(self, plan: _Plan) -> None:
+        self.depth, self.chains, self.group, self.span, self.span_batch = plan
+        # (stream priorities do not help: the device offers only (0, -1), and high-priority side streams measured the same)
+        want = self.chains if self.depth > 1 else 0
+        while len(self.streams) < want:
+            self.streams.append(torch.cuda.Stream())
+        self.streams = self.streams[:want]
 
     def rebind(self, images: torch.Tensor) -> None:
         """A cached pipeline (pipelined_features keeps one per model and mode) meets batches of another shape: choose group / span /
@@ -395,23 +414,25 @@ class FeaturePipeline:
             return
         if self._queue or self._open:
             raise RuntimeError("rebind() needs an empty pipeline")
-        depth = default_depth() if self._depth_arg is None else int(self._depth_arg)
-        if not getattr(self.model, "supports_pipelining", False):
-            depth = 1
-        self.depth, self.group = depth, (1 if depth == 1 else self._group_arg)
-        self.chains = max(1, min(depth, self._streams_arg))
-        while len(self.streams) < (self.chains if depth > 1 else 0):
-            self.streams.append(torch.cuda.Stream())
-        self.streams = self.streams[:self.chains] if depth > 1 else []
-        self.span, self.span_batch, self._span_resolved, self._n = 0, 0, False, 0
+        self._resolved_for, self._n = None, 0
         self.resolve_group(images)
 
     # ------------------------------------------------------------------ one forward on a slot's stream
     def _eager(self, slot: int, images: torch.Tensor, groups: int = 1):
         with _slot((self._ns, slot), self.chains, groups):
-            _take_deferred()
             feats = _extract(self.model, images)
             return feats, _take_deferred()
+
+    def _graph_key(self, slot: int, batches, G):
+        """Key in ``_graphs`` of the graph of a forward over ``batches`` on ``slot``, and the engine that graph is tied to."""
+        eng = self.model.engine() if hasattr(self.model, "engine") else None
+        shape = (sum(b.shape[0] for b in batches),) + tuple(batches[0].shape[1:])
+        return (slot, shape, batches[0].dtype, bool(self.model.training), id(eng), G), eng
+
+    def _new_graph(self, key) -> dict:
+        """The entry of a graph not yet captured (``_capture`` adds graph, static_in, feats, deferred, packs, keep)."""
+        ent = self._graphs[key] = dict(calls=0, graph=None)
+        return ent
 
     def _forward(self, slot: int, s, batches, G):
         """Runs on stream ``s`` (current).  ``batches``: the image tensors of this forward, stacked along dim 0 — G whole batches
@@ -419,9 +440,8 @@ class FeaturePipeline:
         and (batch index, update) pairs covering all the batches the forward completes."""
         first = batches[0]
         is_span = isinstance(G, Span)
-        shape = (sum(b.shape[0] for b in batches),) + tuple(first.shape[1:])
-        eng = self.model.engine() if hasattr(self.model, "engine") else None
-        key = (slot, shape, first.dtype, bool(self.model.training), id(eng), G)
+        key, eng = self._graph_key(slot, batches, G)
+        shape = key[1]
         if is_span:
             # span forwards replay the graph of their (slot, carry) pattern when ``_precapture_spans`` set one up at the pipeline's first
             # submit; anything else (a short span at the stream's end, a stream that restarted out of phase) runs eagerly rather than
@@ -446,7 +466,7 @@ class FeaturePipeline:
                 mine = [k for k in self._graphs if k[0] == slot and not isinstance(k[5], Span)]
                 for k in mine[:-1] if len(mine) >= 2 else []:
                     del self._graphs[k]
-                ent = self._graphs[key] = dict(calls=0, graph=None)
+                ent = self._new_graph(key)
             else:
                 self._graphs[key] = self._graphs.pop(key)  # most recently used last
             ent["calls"] += 1
@@ -457,11 +477,11 @@ class FeaturePipeline:
                 for other in range(self.depth):
                     if other != slot:
                         okey = (other,) + key[1:]
-                        oent = self._graphs[okey] = dict(calls=0, graph=None)
-                        self._capture(other, s, batches, shape, G, oent, eng)
+                        self._new_graph(okey)
+                        self._capture(okey, eng, s, batches)
             if ent["graph"] is None:
-                return self._capture(slot, s, batches, shape, G, ent, eng)  # (its replay computed this forward's features)
-        self._fill(ent["static_in"], batches, G)
+                return self._capture(key, eng, s, batches)  # (its replay computed this forward's features)
+        self._fill(ent["static_in"], batches)
         ent["graph"].replay()
         for pk in ent["packs"]:
             pk.rewritten()  # (the forward's host code, which says so for an eager forward, does not run on a replay)
@@ -477,15 +497,13 @@ class FeaturePipeline:
         filler = []
         while sum(f.shape[0] for f in filler) < T:
             filler.append(sample[:T - sum(f.shape[0] for f in filler)])
-        shape = (T,) + tuple(sample.shape[1:])
-        eng = self.model.engine() if hasattr(self.model, "engine") else None
         for slot, carry in pats:
-            G = Span(B, carry, self._ns)
-            ent = self._graphs[(slot, shape, sample.dtype, bool(self.model.training), id(eng), G)] = dict(calls=0, graph=None)
-            self._capture(slot, s, filler, shape, G, ent, eng)
+            key, eng = self._graph_key(slot, filler, Span(B, carry, self._ns))
+            self._new_graph(key)
+            self._capture(key, eng, s, filler)
 
     @staticmethod
-    def _fill(dst: torch.Tensor, batches, G=None) -> None:
+    def _fill(dst: torch.Tensor, batches) -> None:
         at = 0
         for b in batches:
             dst[at:at + b.shape[0]].copy_(b, non_blocking=True)
@@ -498,29 +516,30 @@ class FeaturePipeline:
         if buf is None:
             self._stage = {k: v for k, v in self._stage.items() if k[0] != slot}
             buf = self._stage[key] = torch.empty(shape, dtype=batches[0].dtype, device=batches[0].device)
-        self._fill(buf, batches, len(batches))
+        self._fill(buf, batches)
         return buf
 
-    def _capture(self, slot: int, s, batches, shape, G: int, ent: dict, eng):
-        """Set a slot up for this input shape: an eager forward (allocates the slot's buffers, builds lazily cached operands — none of
-        that may happen inside a capture), the capture of the very same call, and a first replay on the real input (a graph's first launch
+    def _capture(self, key, eng, s, batches):
+        """Set a slot up for this input shape (``key``, ``eng``: what ``_graph_key`` returned; the entry is ``_graphs[key]``): an eager
+        forward (allocates the slot's buffers, builds lazily cached operands — none of that may happen inside a capture), the capture of the very same call, and a first replay on the real input (a graph's first launch
         uploads it to the device: that cost belongs here, not in the run).  Returns the replay's (features, deferred updates)."""
         from .vit import lookup_pack
 
-        skey = (slot, tuple(shape), batches[0].dtype)  # one static input per slot and shape (a slot's span patterns share it)
+        slot, shape, G = key[0], key[1], key[-1]
+        skey = key[:3]  # (slot, shape, dtype): one static input per slot and shape (a slot's span patterns share it)
         static_in = self._static.get(skey)
         if static_in is None:
             static_in = self._static[skey] = torch.empty(shape, dtype=batches[0].dtype, device=batches[0].device)
-        self._fill(static_in, batches, G)
+        self._fill(static_in, batches)
         self._eager(slot, static_in, G)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):  # other threads (allocator, collectives' watchdog) stay free
             feats, deferred = self._eager(slot, static_in, G)
         per_batch = list(feats) if isinstance(feats, GroupedFeatures) else [feats]
         packs = [pk for pk in (lookup_pack(f) if isinstance(f, (list, tuple)) else None for f in per_batch) if pk is not None]
-        ent.update(graph=g, static_in=static_in, feats=feats, deferred=deferred, packs=packs,
-                   # the graph holds raw addresses of the slot's buffers and of the engine's operands: both stay alive with it
-                   keep=(eng, eng.slot_state((self._ns, slot)) if hasattr(eng, "slot_state") else None))
+        self._graphs[key].update(graph=g, static_in=static_in, feats=feats, deferred=deferred, packs=packs,
+                                 # the graph holds raw addresses of the slot's buffers and of the engine's operands: both stay alive with it
+                                 keep=(eng, eng.slot_state((self._ns, slot)) if hasattr(eng, "slot_state") else None))
         g.replay()
         return feats, deferred
 
@@ -649,6 +668,89 @@ def cached_pipelines(model) -> dict:
         return _NO_CACHE
 
 
+def _images_of(b, image_key):
+    x = b[image_key] if isinstance(b, dict) else b[0]
+    if x.is_cuda or not torch.cuda.is_available():  # (a host tensor without a device: the backbone raises MvpError)
+        return x
+    return x.to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+
+
+class _Feeder:
+    """Cuts a stream of batches into the forwards of ``pipe``'s plan: groups of ``pipe.group`` consecutive equal-shaped batches, or —
+    for batches of ``pipe.span_batch`` images when the plan has a span — ``pipe.span`` images that may end in the middle of a batch.
+    An epoch's ragged last batch, a change of shape and the end of the stream end a forward early.  Pulls a batch from the stream only
+    when a forward needs it."""
+
+    def __init__(self, pipe, batches: Iterable, image_key="image", rebind: bool = False):
+        self.pipe, self.it, self.image_key = pipe, iter(batches), image_key
+        self.rebind = rebind  # a pipeline taken from the model's cache may have been shaped for other batches: ask it at the first one
+        self.held = None  # (batch, images) pulled from the iterator that did not fit the forward being formed
+        self.cut = None   # (batch, images, images of it already forwarded): the batch the previous span forward ended in
+
+    def _pull(self):
+        if self.held is not None:
+            nxt, self.held = self.held, None
+            return nxt
+        try:
+            b = next(self.it)
+        except StopIteration:
+            return None
+        return b, _images_of(b, self.image_key)
+
+    def next_forward(self):
+        """The next forward as ``(batches it completes, image tensors, None)`` for ``submit_group`` or ``(batches it completes, pieces,
+        (B, carry))`` for ``submit_span``; None at the end of the stream."""
+        if self.cut is not None:
+            return self._span()
+        first = self._pull()
+        if first is None:
+            return None
+        if self.rebind:
+            self.rebind = False
+            self.pipe.rebind(first[1])
+        G = self.pipe.resolve_group(first[1])
+        if self.pipe.span and first[1].shape[0] == self.pipe.span_batch:
+            self.held = first
+            return self._span()
+        grp = [first]
+        while len(grp) < G:
+            nxt = self._pull()
+            if nxt is None:
+                break
+            if nxt[1].shape != first[1].shape or nxt[1].dtype != first[1].dtype:
+                self.held = nxt
+                break
+            grp.append(nxt)
+        return [b for b, _ in grp], [x for _, x in grp], None
+
+    def _span(self):
+        """One forward over the next ``pipe.span`` images of the stream (fewer at its end or where the batch shape changes)."""
+        B = self.pipe.span_batch
+        pieces, done, carry, room = [], [], 0, self.pipe.span
+        if self.cut is not None:
+            (b, x, used), self.cut = self.cut, None
+            pieces.append(x[used:])  # (a span is longer than a batch: the cut batch always completes here)
+            done.append(b)
+            carry, room = used, room - (B - used)
+        while room > 0:
+            nxt = self._pull()
+            if nxt is None:
+                break
+            ref = pieces[0] if pieces else None
+            if nxt[1].shape[0] != B or (ref is not None and (nxt[1].shape[1:] != ref.shape[1:] or nxt[1].dtype != ref.dtype)):
+                self.held = nxt  # (the span ends on a batch boundary here: a batch is only ever cut as the last piece)
+                break
+            if room >= B:
+                pieces.append(nxt[1])
+                done.append(nxt[0])
+                room -= B
+            else:
+                pieces.append(nxt[1][:room])
+                self.cut = (nxt[0], nxt[1], room)
+                room = 0
+        return done, pieces, (B, carry)
+
+
 def pipelined_features(model, batches: Iterable, image_key="image", depth: int = None, probe=None, group: int = None,
                        pipe: "FeaturePipeline" = None, graphs: bool = None) -> Iterator[Tuple[object, object]]:
     """Yield ``(batch, features)`` for every batch of ``batches`` with up to ``depth`` forwards in flight: the forwards of the next
@@ -692,96 +794,20 @@ def pipelined_features(model, batches: Iterable, image_key="image", depth: int =
         if lent is not None and pipe._resolved_for is not None:
             g_hold = max(g_hold, MAX_GROUP + 1)  # a cached pipeline may be re-shaped by this loader's first batch (rebind)
         batches.consumer_lag = max(int(batches.consumer_lag), pipe.depth * g_hold - 1)
-    it = iter(batches)
-    pending = collections.deque()
-    held = []  # a batch pulled from the iterator that did not fit the group being formed
-
-    def images_of(b):
-        x = b[image_key] if isinstance(b, dict) else b[0]
-        if x.is_cuda or not torch.cuda.is_available():  # (a host tensor without a device: the backbone raises MvpError)
-            return x
-        return x.to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
-
-    def pull():
-        if held:
-            return held.pop()
-        try:
-            b = next(it)
-        except StopIteration:
-            return None
-        return b, images_of(b)
-
-    cut = []  # [(batch, images, images of it already forwarded)]: the batch the previous span forward ended in
-
-    def feed_span() -> bool:
-        """One forward over the next ``pipe.span`` images of the stream (fewer at its end or where the batch shape changes)."""
-        B = pipe.span_batch
-        pieces, done, carry, room = [], [], 0, pipe.span
-        if cut:
-            b, x, used = cut.pop()
-            pieces.append(x[used:])  # (a span is longer than a batch: the cut batch always completes here)
-            done.append(b)
-            carry, room = used, room - (B - used)
-        while room > 0:
-            nxt = pull()
-            if nxt is None:
-                break
-            ref = pieces[0] if pieces else None
-            if nxt[1].shape[0] != B or (ref is not None and (nxt[1].shape[1:] != ref.shape[1:] or nxt[1].dtype != ref.dtype)):
-                held.append(nxt)  # (the span ends on a batch boundary here: a batch is only ever cut as the last piece)
-                break
-            if room >= B:
-                pieces.append(nxt[1])
-                done.append(nxt[0])
-                room -= B
-            else:
-                pieces.append(nxt[1][:room])
-                cut.append((nxt[0], nxt[1], room))
-                room = 0
-        if not pieces:
-            return False
-        if not done:  # part of one batch and nothing else (cannot happen: spans are longer than a batch): run the batch whole
-            b, x, _ = cut.pop()
-            pipe.submit_group([x])
-            pending.append(b)
-            return True
-        pipe.submit_span(pieces, B, carry)
-        pending.extend(done)
-        return True
-
-    started = []
-
-    def feed() -> bool:
-        if cut:
-            return feed_span()
-        first = pull()
-        if first is None:
-            return False
-        if not started:  # a pipeline taken from the model's cache may have been shaped for other batches
-            started.append(True)
-            if lent is not None:
-                pipe.rebind(first[1])
-        G = pipe.resolve_group(first[1])
-        if pipe.span and first[1].shape[0] == pipe.span_batch:
-            held.append(first)
-            return feed_span()
-        grp = [first]
-        while len(grp) < G:
-            nxt = pull()
-            if nxt is None:
-                break
-            if nxt[1].shape != first[1].shape or nxt[1].dtype != first[1].dtype:
-                held.append(nxt)
-                break
-            grp.append(nxt)
-        pipe.submit_group([x for _, x in grp])
-        pending.extend(b for b, _ in grp)
-        return True
-
+    feeder = _Feeder(pipe, batches, image_key, rebind=lent is not None)
+    pending = collections.deque()  # batches of the forwards in flight, in the order they are handed over
     try:
         while True:
-            while pipe.free_slots() > 0 and feed():
-                pass
+            while pipe.free_slots() > 0:
+                fwd = feeder.next_forward()
+                if fwd is None:
+                    break
+                done, images, span = fwd
+                if span is None:
+                    pipe.submit_group(images)
+                else:
+                    pipe.submit_span(images, *span)
+                pending.extend(done)
             if not pending:
                 break
             b = pending.popleft()
