@@ -105,6 +105,9 @@ typedef struct {
                                 Added within 8: mvp_swiglu_fwd (the gate of DINOv2's SwiGLU MLP, silu(x1) * x2 between the w12 and w3 GEMMs of
                                 ViT-g/14, written as the zero-padded A operand pair of w3); a new export with its own tagged argument struct,
                                 no existing struct changed.
+                                Added within 8: mvp_task_prepare, mvp_masked_l1_fwd_bwd and mvp_task_metrics (Taskonomy probing: raw target and
+                                valid mask on the device, masked L1 loss, AbsRel / threshold sums); new exports with their own tagged argument
+                                structs, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -1317,6 +1320,74 @@ struct mvp_swiglu_args {
   int out_f16;                        /* 1: the pair is the activation operand of MVP_PREC_F16X2, as mvp_layernorm_args.out_f16      */
 };
 int mvp_swiglu_fwd(const mvp_swiglu_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; new exports with their own tagged argument structs, no existing struct changed.)
+ * The task-specific ends of Taskonomy probing (evals/datasets/transforms.py task_transform / make_valid_mask, evals/utils/losses.py:77-94
+ * MaskedL1Loss, evals/utils/metrics.py:580-739).  All reductions: per-workgroup fp64 partials in the workspace, folded in a fixed
+ * order, no float atomics; two calls give the same bits.  One workspace size serves the loss and the metrics.
+ *
+ * mvp_task_prepare: the raw target and the raw mask, as a decoder leaves them, -> the training tensors.
+ *   target_raw  bits = 8: uint8 [B, H, W, Cs], the first Ct channels kept;  bits = 16: uint16 [B, H, W] (Cs = Ct = 1).
+ *   mask_raw    uint8 [B, H, W]
+ *   target      fp32 [B, Ct, H, W] = k / 255 or k / 65535, a correctly rounded fp32 division; clamp_max > 0 (the task's clamp_to
+ *               (0, maxx)): then min(max(x, 0), clamp_max) / clamp_max, correctly rounded again.
+ *   valid       uint8 [B, 1, H, W], 0 or 1: make_valid_mask.  With hp = H / 4, wp = W / 4 (integer), pixel (y, x) is valid iff all 16
+ *               raw mask values of rows 4i .. 4i+3, columns 4j .. 4j+3 equal 255, (i, j) = ((y hp) / H, (x wp) / W).  Rows and columns
+ *               from 4 hp / 4 wp on belong to no block: what they hold invalidates nothing, and they read a block through the map.
+ *   H % 4 == 0, W % 4 == 0, Cs <= 4 and aligned bases (16 bytes target, 8 the 16-bit raw target, 4 the rest): 16-byte stores, 4-byte
+ *   mask words; anything else one pixel per thread.
+ *   MVP_EINVAL: a NULL pointer, B <= 0, H < 4 or W < 4 (the reference's pooling has no output), Ct < 1, Cs < Ct, bits not 8 or 16,
+ *   bits = 16 with Cs != 1, clamp_max < 0 or NaN.
+ *
+ * mvp_masked_l1_fwd_bwd: pred, target fp32 [B, C, HW]; valid uint8 [B, Cm, HW], Cm = 1 (one mask for every channel) or C.
+ *   loss[0] = sum valid |pred - target| / (sum valid * C / Cm): differences taken in fp64 (exact), summed in fp64, one rounding to
+ *   fp32.  grad_pred [B, C, HW] (NULL: loss only) = sign(pred - target) * fp32(1 / count) where valid, exactly 0 elsewhere (a select;
+ *   sign(0) = 0).  No valid pixel: the loss is NaN (0 / 0, as the reference) and the gradient all zeros.  Two launches: the count
+ *   is complete before the gradient is written.
+ *   MVP_EINVAL: a NULL pointer other than grad_pred, B, C or HW <= 0, Cm not 1 or C, workspace_bytes < MVP_TASK_WORKSPACE_BYTES or
+ *   the workspace not 8-byte aligned.
+ *
+ * mvp_task_metrics: pred, target fp32 [B, C, HW], valid as above -> out fp64 [B, C, 5] =
+ *   (sum absrel * v, sum v, n(ratio < t1), n(ratio < t2), n(ratio < t3)), v the mask as 0.0 / 1.0; a pixel is counted iff valid and
+ *   ratio < t.  Every fp32 tensor operation of the reference is one separately rounded fp32 operation here (no FMA); the terms are
+ *   widened to fp64 before they are summed.
+ *   MVP_TASK_METRICS_CURVATURE (evaluate_curvature_absrel): p = clamp(pred, -1, 1) (NaN stays), absrel = |p - g| / |g + 1e-6f|,
+ *       ratio = max(p / g, g / p), NaN if either quotient is; negative ratios count (a quirk of the reference).
+ *   MVP_TASK_METRICS_RESHADING (evaluate_reshading_absrel_and_delta): p = pred * v, t = target * v, absrel = |p - t| / (t + 1e-6f),
+ *       ratio = max(p / (t + 1e-6f), t / (p + 1e-6f)).
+ *   absrel is MULTIPLIED by v: a non-finite value at an invalid pixel makes the image's sum NaN, as in the reference.
+ *   MVP_EINVAL: a NULL pointer, B, C or HW <= 0, B * C > 1024, Cm not 1 or C, an unknown form, workspace_bytes <
+ *   MVP_TASK_WORKSPACE_BYTES, workspace or out not 8-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+#define MVP_TASK_WORKSPACE_BYTES 40960 /* 1024 partial rows x 5 fp64 */
+#define MVP_TASK_METRICS_CURVATURE 0
+#define MVP_TASK_METRICS_RESHADING 1
+typedef struct mvp_task_prepare_args mvp_task_prepare_args;
+struct mvp_task_prepare_args {
+  const void* target_raw; const uint8_t* mask_raw; float* target; uint8_t* valid;
+  int B, H, W, Cs, Ct, bits;
+  float clamp_max;
+};
+int mvp_task_prepare(const mvp_task_prepare_args*, void* stream);
+
+typedef struct mvp_masked_l1_args mvp_masked_l1_args;
+struct mvp_masked_l1_args {
+  const float* pred; const float* target; const uint8_t* valid; float* loss; float* grad_pred;
+  void* workspace; int64_t workspace_bytes;
+  int B, C, Cm; int64_t HW;
+};
+int mvp_masked_l1_fwd_bwd(const mvp_masked_l1_args*, void* stream);
+
+typedef struct mvp_task_metrics_args mvp_task_metrics_args;
+struct mvp_task_metrics_args {
+  const float* pred; const float* target; const uint8_t* valid; double* out;
+  void* workspace; int64_t workspace_bytes;
+  int B, C, Cm; int64_t HW;
+  int form;
+  float t1, t2, t3;
+};
+int mvp_task_metrics(const mvp_task_metrics_args*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,7 @@ extern "C" int mvp_sizeof(const char* name) {
   MVP_SZ(mvp_crf_filter_args) MVP_SZ(mvp_crf_update_args) MVP_SZ(mvp_mask_finish_args)
   MVP_SZ(mvp_augment_stats_args) MVP_SZ(mvp_augment_apply_args)
   MVP_SZ(mvp_swiglu_args)
+  MVP_SZ(mvp_task_prepare_args) MVP_SZ(mvp_masked_l1_args) MVP_SZ(mvp_task_metrics_args)
 #undef MVP_SZ
   return -1;
 }

@@ -1,7 +1,11 @@
 """build_loader with the reference's semantics (evals/datasets/builder.py:39-67): DistributedSampler iff num_gpus > 1,
 shuffle only for the single-process train split, drop_last=False, pin_memory=True.  The reference hard-codes
 num_workers=0 (builder.py:53-54); here it is a keyword (default 0 = identical behaviour) because once the step takes
-3 ms the decode + collate of the next batch must overlap it (mvp.prefetch.DevicePrefetcher does the H2D side)."""
+3 ms the decode + collate of the next batch must overlap it (mvp.prefetch.DevicePrefetcher does the H2D side).
+
+A dataset node that carries ``task:`` is a Taskonomy dataset (builder.py:47-49): with a ``_target_`` the instantiated dataset is wrapped
+in evals.datasets.taskonomy.TaskonomyDataset(dataset, task), which applies the per-sample transforms on the host; without one it is
+evals.datasets.synthetic.SyntheticTaskonomy (``raw: true``: undecoded bytes for mvp.taskonomy.DeviceTaskTransform)."""
 from __future__ import annotations
 
 import torch
@@ -16,7 +20,15 @@ def _make_dataset(cfg, split, **kwargs):
 
     node = dict(cfg)
     if "task" in node:
-        raise NotImplementedError("TaskonomyDataset wrapping (builder.py:47-49) is outside the hot path")
+        if "_target_" not in node:  # configs/dataset/synthetic_taskonomy.yaml style
+            from .synthetic import SyntheticTaskonomy
+
+            opts = {k: node[k] for k in ("num_samples", "image_size", "raw", "seed", "name", "image_mean") if k in node}
+            return SyntheticTaskonomy(split=split, task=node["task"], **opts, **kwargs)
+        from .taskonomy import TaskonomyDataset
+
+        # builder.py:47-49: the instantiated dataset (which receives `task` like every other key) wrapped per sample
+        return TaskonomyDataset(config.instantiate(node, split=split, **kwargs), node["task"])
     if "_target_" not in node:  # configs/dataset/synthetic.yaml style
         from .synthetic import SyntheticNYU, SyntheticNYURaw
 

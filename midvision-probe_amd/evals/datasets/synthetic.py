@@ -103,3 +103,71 @@ class SyntheticNYURaw(SyntheticNYU):
         rgb = rgb + 0.02 * torch.randn(3, H, W, generator=g)
         out["image"] = (rgb.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).permute(1, 2, 0).contiguous()
         return out
+
+
+class SyntheticTaskonomy(Dataset):
+    """Taskonomy-shaped synthetic samples for one task of mvp.taskonomy.TASKS.  ``raw=True``: what a PNG decoder hands over — "rgb" uint8
+    [H, W, 3]; the task's target uint8 [H, W, Cs] (8-bit tasks: Cs = 3 stored channels for principal_curvature and normal, 1 for
+    reshading) or int16 [H, W] holding the uint16 bit patterns (16-bit tasks; torch batches carry no uint16); "mask_valid" uint8 [H, W]
+    with 255 = valid.  ``raw=False``: the same sample through evals.datasets.transforms.task_transform — the reference's item contract
+    {"rgb": float32 [3, H, W] normalised, task: float32 [Ct, H, W], "mask_valid": bool [1, H, W]}.
+
+    About a tenth of each mask is invalid, in five ellipses whose borders cross the 4 x 4 blocks make_valid_mask grows them to; the
+    targets are a smooth field plus noise with exact zeros sprinkled in (AbsRel's denominator then is the 1e-6 alone).  Samples are a pure
+    function of (seed, split, task, index)."""
+
+    def __init__(self, split: str = "train", task: str = "principal_curvature", num_samples: int = 64, image_size=(512, 512), raw: bool = True,
+                 seed: int = 0, name: str = "taskonomy", image_mean="imagenet"):
+        from mvp.taskonomy import resolve_task
+
+        if split not in ("train", "valid", "val", "test"):
+            raise ValueError(f"SyntheticTaskonomy: split {split!r}")
+        self.kernel_task, self.spec = resolve_task("depth_euclidean" if task == "depth" else task)
+        self.split, self.task, self.n = split, task, int(num_samples)
+        self.hw = (int(image_size), int(image_size)) if isinstance(image_size, int) else tuple(int(v) for v in image_size)
+        self.raw, self.seed, self.name, self.image_mean = bool(raw), int(seed), name, image_mean
+        self._salt = {"train": 0, "valid": 1, "val": 1, "test": 2}[split]
+
+    def __len__(self) -> int:
+        return self.n
+
+    def __getitem__(self, i: int):
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        g = torch.Generator().manual_seed((self.seed * 4 + self._salt) * 1_000_003 + i + 33_000_000)
+        H, W = self.hw
+        ys = torch.linspace(0.0, 1.0, H).view(H, 1)
+        xs = torch.linspace(0.0, 1.0, W).view(1, W)
+        u = torch.rand(3, 3, generator=g)
+        rgb = torch.stack([(u[c, 0] * xs + u[c, 1] * ys) * 0.5 + 0.25 * u[c, 2] for c in range(3)]) + 0.05 * torch.randn(3, H, W, generator=g)
+        rgb = (rgb.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).permute(1, 2, 0).contiguous()
+        # the target follows the image (something to learn) with its own noise
+        bits, ct = int(self.spec["bits"]), int(self.spec["channels"])
+        cs = 1 if bits == 16 or ct == 1 else 3
+        base = rgb.permute(2, 0, 1).float()[:cs] / 255.0
+        field = (0.6 * base + 0.25 + 0.1 * torch.randn(cs, H, W, generator=g)).clamp(0.0, 1.0)
+        if self.spec["clamp"] is not None:
+            field = field * (2.0 * float(self.spec["clamp"]))  # half of the values above the clamp
+        top = 255.0 if bits == 8 else 65535.0
+        k = (field * top).round().to(torch.int32)
+        k[torch.rand(cs, H, W, generator=g) < 0.02] = 0
+        if bits == 8:
+            target = k.to(torch.uint8).permute(1, 2, 0).contiguous()
+        else:
+            target = torch.where(k[0] >= 32768, k[0] - 65536, k[0]).to(torch.int16).contiguous()
+        mask = torch.full((H, W), 255, dtype=torch.uint8)
+        yy = torch.arange(H, dtype=torch.float32).view(H, 1)
+        xx = torch.arange(W, dtype=torch.float32).view(1, W)
+        for _ in range(5):
+            v = torch.rand(3, generator=g)
+            f = 0.7 + 0.7 * float(v[2])
+            ry, rx = max(H * 0.0798 * f, 0.75), max(W * 0.0798 / f, 0.75)  # pi ry rx = 2 % of the image
+            cy, cx = float(v[0]) * (H - 1), float(v[1]) * (W - 1)
+            mask[((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1.0] = 0
+        sample = {"rgb": rgb, self.task: target, "mask_valid": mask}
+        if self.raw:
+            return sample
+        from .transforms import task_transform
+
+        return {"rgb": task_transform(rgb, "rgb", self.image_mean), self.task: task_transform(target, self.kernel_task),
+                "mask_valid": task_transform(mask, "mask_valid")}

@@ -1,5 +1,5 @@
-"""evals.utils.losses — drop-in for the losses the two trainers use
-(evals/utils/losses.py:54-74,97-182), forward + analytic backward in HIP kernels."""
+"""evals.utils.losses — drop-in for the losses the trainers use
+(evals/utils/losses.py:54-74,77-94,97-182), forward + analytic backward in HIP kernels."""
 from __future__ import annotations
 
 import torch.nn as nn
@@ -17,6 +17,16 @@ class DepthLoss(nn.Module):
 
     def forward(self, pred, target):
         return MF.depth_loss(pred, target, self.sig_w, self.grad_w, self.max_depth)
+
+
+class MaskedL1Loss(nn.Module):
+    """Reference: losses.py:77-94.  ``mask_valid`` None: every element counts; a one-channel mask is repeated over the channels."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, preds, target, mask_valid=None):
+        return MF.masked_l1_loss(preds, target, mask_valid)
 
 
 def sig_loss(depth_pr, depth_gt, sigma=0.85, eps=0.001, only_mean=False):

@@ -168,3 +168,68 @@ def evaluate_surface_norm(snorm_pr, snorm_gt, segmentation_map=None, image_avera
         gm = {k: v.mean() for k, v in gm.items()}
         levels = {L: {k: v.mean() for k, v in d.items()} for L, d in levels.items()}
     return gm, levels, segments
+
+
+# --------------------------------------------------------------------------- Taskonomy: AbsRel and threshold accuracies
+def task_metric_sums(pred, target, valid, form, thresholds):
+    """fp64 [B, C, 5] ON THE DEVICE = (sum absrel v, sum v, n < t1, n < t2, n < t3) per image and channel (csrc/taskonomy.hip).
+    ``form``: "curvature" or "reshading"; ``thresholds``: three numbers, compared in fp32 as torch compares an fp32 tensor with a
+    Python float."""
+    from mvp import functional as MF
+    from mvp import ops
+
+    if not (pred.is_cuda and target.is_cuda and valid.is_cuda):
+        raise lib.MvpError("metrics need device tensors (no CPU fallback)")
+    assert pred.shape == target.shape, f"{pred.shape} != {target.shape}"
+    B, Cdim = pred.shape[:2]
+    HW = pred.numel() // (B * Cdim)
+    p = pred.detach().reshape(B, Cdim, HW).contiguous().float()
+    g = target.detach().reshape(B, Cdim, HW).contiguous().float()
+    m = MF.valid_bytes(valid, B, HW)
+    if m.shape[1] not in (1, Cdim):
+        raise ValueError(f"the mask {tuple(valid.shape)} must have 1 or {Cdim} channels")
+    out = torch.empty(B, Cdim, 5, dtype=torch.float64, device=p.device)
+    t32 = [float(torch.tensor(float(t), dtype=torch.float32)) for t in thresholds]
+    ops.task_metrics(p, g, m, out, ops.task_workspace(p.device), B, Cdim, m.shape[1], HW, form, t32)
+    return out
+
+
+def _per_image(sums):
+    """[B, C, 5] fp64 (host) -> AbsRel [B, C], accuracies [B, C, 3]: sums over max(valid pixels, 1)."""
+    n = sums[..., 1].clamp(min=1)
+    return sums[..., 0] / n, sums[..., 2:5] / n.unsqueeze(-1)
+
+
+def evaluate_curvature_absrel(norm_curvature, norm_gt_curvature, valid, image_average=False):
+    """Reference: metrics.py:580-678 (the first two channels of the prediction, clamped to [-1, 1]; thresholds 1.25, 2.5, 3.75 per
+    principal curvature and averaged).  Returns the reference's dict of [B] CPU tensors (scalars with ``image_average``)."""
+    pred = norm_curvature[:, :2]
+    sums = task_metric_sums(pred, norm_gt_curvature, valid, "curvature", (1.25, 1.25 * 2, 1.25 * 3)).cpu()
+    absrel, acc = _per_image(sums)
+    metrics = {"AbsRel": ((absrel[:, 0] + absrel[:, 1]) / 2).float()}
+    for c, k in ((0, "k1"), (1, "k2")):
+        for j, t in enumerate(("1.25", "2.5", "3.75")):
+            metrics[f"δ{t}_{k}"] = acc[:, c, j].float()
+    for j, t in enumerate(("1.25", "2.5", "3.75")):
+        metrics[f"δ{t}_avg"] = ((acc[:, 0, j] + acc[:, 1, j]) / 2).float()
+    if image_average:
+        metrics = {k: v.mean() for k, v in metrics.items()}
+    return metrics
+
+
+def evaluate_reshading_absrel_and_delta(pred, target, mask, thresholds=[1.1, 1.1**2, 1.1**3], image_average=False):
+    """Reference: metrics.py:681-739 for one-channel maps [B, 1, H, W]; the keys are the reference's f"δ_{threshold}" strings
+    ("δ_1.2100000000000002" for 1.1**2).  Returns [B] tensors on the host (the reference leaves them on the inputs' device)."""
+    if pred.dim() == 4 and pred.shape[1] != 1:
+        raise ValueError(f"evaluate_reshading_absrel_and_delta takes one-channel maps, got {tuple(pred.shape)}")
+    if len(thresholds) != 3:
+        raise NotImplementedError("three thresholds are compiled in")
+    B = pred.shape[0]
+    sums = task_metric_sums(pred.reshape(B, 1, -1), target.reshape(B, 1, -1), mask.reshape(B, 1, -1), "reshading", thresholds).cpu()
+    absrel, acc = _per_image(sums)
+    metrics = {"AbsRel": absrel[:, 0].float()}
+    for j, t in enumerate(thresholds):
+        metrics[f"δ_{t}"] = acc[:, 0, j].float()
+    if image_average:
+        metrics = {k: v.mean() for k, v in metrics.items()}
+    return metrics

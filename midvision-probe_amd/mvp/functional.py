@@ -7,6 +7,7 @@ the HIP kernels through the C ABI; PyTorch only provides the tape, memory and st
   depth_bins / depth_sigmoid   probes.py:176-212
   depth_loss / angular_loss    evals/utils/losses.py:97-182
   bn_act / bce_loss            probes.py:36-43 (BinaryHead's BatchNorm2d + sigmoid), train_generic_objectness.py:395 (nn.BCELoss)
+  masked_l1_loss               evals/utils/losses.py:77-94 (MaskedL1Loss, Taskonomy probing)
 """
 from __future__ import annotations
 
@@ -592,3 +593,49 @@ class _BceLoss(torch.autograd.Function):
 def bce_loss(pred, target):
     """``nn.BCELoss()(pred, target)`` (mean; log terms clamped at -100) with its gradient from the same launch chain."""
     return _BceLoss.apply(pred, target)
+
+
+# --------------------------------------------------------------------------- Taskonomy: masked L1
+def valid_bytes(mask: torch.Tensor, B: int, HW: int) -> torch.Tensor:
+    """A [B, Cm, ...] mask (bool, uint8 or float, nonzero = valid) as the contiguous uint8 [B, Cm, HW] the kernels read."""
+    m = mask.detach().reshape(B, -1, HW)
+    if m.dtype != torch.uint8:
+        m = (m != 0).to(torch.uint8)
+    return m.contiguous()
+
+
+class _MaskedL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, valid, need_grad):
+        _need_cuda(pred, "masked_l1_loss")
+        if tuple(pred.shape) != tuple(target.shape):
+            raise ValueError(f"masked_l1_loss: prediction {tuple(pred.shape)} and target {tuple(target.shape)} differ")
+        B, Cdim = pred.shape[:2]
+        HW = pred.numel() // (B * Cdim)
+        p = pred.contiguous().float()
+        t = target.contiguous().float()
+        if valid is None:
+            m = torch.ones(B, 1, HW, dtype=torch.uint8, device=p.device)
+        else:
+            m = valid_bytes(valid, B, HW)
+        if m.shape[1] not in (1, Cdim) or not m.is_cuda:
+            raise ValueError(f"masked_l1_loss: the mask {tuple(m.shape)} must be a device tensor with 1 or {Cdim} channels over the prediction's pixels")
+        out = torch.empty(1, dtype=torch.float32, device=p.device)
+        # no gradient asked for (validation under no_grad, a detached prediction): the loss-only form, one pass instead of two
+        grad = torch.empty_like(p) if need_grad else None
+        ops.masked_l1(p, t, m, out, grad, ops.task_workspace(p.device), B, Cdim, m.shape[1], HW)
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return _scaled(grad, g), None, None, None
+
+
+def masked_l1_loss(pred, target, valid=None):
+    """``MaskedL1Loss()(pred, target, valid)`` (losses.py:77-94: the sum of |pred - target| over valid elements / their count; a
+    one-channel mask serves every channel; no valid element: NaN) with its gradient from the same launch chain."""
+    # (decided here: inside a Function's forward the grad mode is always off)
+    return _MaskedL1.apply(pred, target, valid, bool(torch.is_grad_enabled() and pred.requires_grad))

@@ -261,6 +261,21 @@ class SwigluArgs(Struct, c_name="mvp_swiglu_args"):  # DINOv2 ViT-g/14: silu(gat
                 ("out_layout", _i), ("out_f16", _i)]
 
 
+class TaskPrepareArgs(Struct, c_name="mvp_task_prepare_args"):  # Taskonomy: raw target + raw mask -> training tensors (added within ABI 8)
+    _fields_ = [("target_raw", _vp), ("mask_raw", _vp), ("target", _vp), ("valid", _vp), ("B", _i), ("H", _i), ("W", _i), ("Cs", _i), ("Ct", _i),
+                ("bits", _i), ("clamp_max", _f)]
+
+
+class MaskedL1Args(Struct, c_name="mvp_masked_l1_args"):  # MaskedL1Loss and its gradient (added within ABI 8)
+    _fields_ = [("pred", _vp), ("target", _vp), ("valid", _vp), ("loss", _vp), ("grad_pred", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+                ("B", _i), ("C", _i), ("Cm", _i), ("HW", _i64)]
+
+
+class TaskMetricsArgs(Struct, c_name="mvp_task_metrics_args"):  # per-image AbsRel / threshold sums of the Taskonomy metrics (added within ABI 8)
+    _fields_ = [("pred", _vp), ("target", _vp), ("valid", _vp), ("out", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+                ("B", _i), ("C", _i), ("Cm", _i), ("HW", _i64), ("form", _i), ("t1", _f), ("t2", _f), ("t3", _f)]
+
+
 class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -429,6 +444,9 @@ SYMBOLS = {
     "mvp_augment_stats": AugmentStatsArgs,
     "mvp_augment_apply": AugmentApplyArgs,
     "mvp_swiglu_fwd": SwigluArgs,
+    "mvp_task_prepare": TaskPrepareArgs,
+    "mvp_masked_l1_fwd_bwd": MaskedL1Args,
+    "mvp_task_metrics": TaskMetricsArgs,
 }
 
 # the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)

@@ -760,3 +760,51 @@ def augment_apply(image, depth, snorm, params, partials, out_image, out_depth, o
     planes = 4 + (3 if snorm is not None else 0)
     work = float(B * H * W * (3 if u8 else 12) + B * H * W * 4 * (planes - 3) + B * Ho * Wo * 4 * planes)
     _traced("hbm", "augment_apply", 0, work, lambda: lib.call("mvp_augment_apply", a))
+
+
+# --------------------------------------------------------------------------- Taskonomy probing (csrc/taskonomy.hip)
+_TASK_WS_BYTES = 40960  # MVP_TASK_WORKSPACE_BYTES
+TASK_METRICS_FORMS = {"curvature": 0, "reshading": 1}  # MVP_TASK_METRICS_*
+
+
+def task_workspace(device) -> torch.Tensor:
+    """A workspace for masked_l1 / task_metrics (MVP_TASK_WORKSPACE_BYTES of fp64 partials; no initialisation needed)."""
+    return torch.empty(_TASK_WS_BYTES // 8, dtype=torch.float64, device=device)
+
+
+def task_prepare(target_raw, mask_raw, target, valid, bits: int, clamp_max: float = 0.0) -> None:
+    """Raw uint8 [B, H, W, Cs] (bits 8) or 16-bit [B, H, W] (bits 16; an int16 tensor holding the uint16 patterns) target and raw uint8
+    [B, H, W] mask -> target fp32 [B, Ct, H, W], valid uint8 [B, 1, H, W] (include/mvp_hip.h: mvp_task_prepare)."""
+    _chk(mask_raw, torch.uint8, "mask_raw")
+    _chk(target_raw, torch.uint8 if bits == 8 else torch.int16, "target_raw")
+    _chk(target, torch.float32, "target")
+    _chk(valid, torch.uint8, "valid")
+    B, H, W = mask_raw.shape
+    Cs = target_raw.shape[3] if bits == 8 else 1
+    Ct = target.shape[1]
+    if tuple(target_raw.shape[:3]) != (B, H, W) or tuple(target.shape) != (B, Ct, H, W) or valid.numel() != B * H * W:
+        raise lib.MvpError(f"task_prepare: shapes disagree: raw {tuple(target_raw.shape)}, mask {tuple(mask_raw.shape)}, "
+                           f"target {tuple(target.shape)}, valid {tuple(valid.shape)}")
+    a = lib.TaskPrepareArgs(lib.ptr(target_raw), lib.ptr(mask_raw), lib.ptr(target), lib.ptr(valid), B, H, W, Cs, Ct, bits, clamp_max)
+    # algorithmic HBM bytes: the raw target and mask read once, the fp32 target and the byte mask written once
+    work = float(B * H * W * (Cs * (bits // 8) + 1 + 4 * Ct + 1))
+    _traced("hbm", "task_prepare", 0, work, lambda: lib.call("mvp_task_prepare", a))
+
+
+def masked_l1(pred, target, valid, loss, grad_pred, workspace, B: int, Cdim: int, Cm: int, HW: int) -> None:
+    """MaskedL1Loss of pred / target [B, C, HW] under valid uint8 [B, Cm, HW] and its gradient (grad_pred may be None):
+    mvp_masked_l1_fwd_bwd."""
+    a = lib.MaskedL1Args(lib.ptr(pred), lib.ptr(target), lib.ptr(valid), lib.ptr(loss), lib.ptr(grad_pred), lib.ptr(workspace),
+                         workspace.numel() * workspace.element_size(), B, Cdim, Cm, HW)
+    # pred, target and the mask are read twice when the gradient is written (the count comes first), once otherwise
+    n = B * Cdim * HW
+    work = float(2 * (8 * n + n) + 4 * n) if grad_pred is not None else float(9 * n)
+    _traced("hbm", "masked_l1", 0, work, lambda: lib.call("mvp_masked_l1_fwd_bwd", a))
+
+
+def task_metrics(pred, target, valid, out, workspace, B: int, Cdim: int, Cm: int, HW: int, form: str, thresholds) -> None:
+    """out fp64 [B, C, 5] = (sum absrel v, sum v, n < t1, n < t2, n < t3) per image and channel: mvp_task_metrics."""
+    a = lib.TaskMetricsArgs(lib.ptr(pred), lib.ptr(target), lib.ptr(valid), lib.ptr(out), lib.ptr(workspace),
+                            workspace.numel() * workspace.element_size(), B, Cdim, Cm, HW, TASK_METRICS_FORMS[form],
+                            thresholds[0], thresholds[1], thresholds[2])
+    _traced("hbm", "task_metrics", 0, float(B * Cdim * HW * 9), lambda: lib.call("mvp_task_metrics", a))

@@ -1,6 +1,8 @@
-"""The hot loop bodies of train_depth.py:93-144, train_snorm.py:86-120 and train_generic_objectness.py:372-398, on the HIP path.
+"""The hot loop bodies of train_depth.py:93-144, train_snorm.py:86-120 and train_generic_objectness.py:372-398, on the HIP path, and
+the loop body of Taskonomy probing, for which the reference ships every part but the loop.
 
-``train_depth_step`` / ``train_snorm_step`` / ``train_objectness_step`` are the per-batch bodies (bench.py times the first);
+``train_depth_step`` / ``train_snorm_step`` / ``train_objectness_step`` / ``train_taskonomy_step`` are the per-batch bodies (bench.py
+times the first);
 ``train`` mirrors the reference's ``train()`` signature for drop-in use.
 """
 from __future__ import annotations
@@ -96,6 +98,28 @@ def train_objectness_step(model, probe, optimizer, scheduler, images, target, de
     pred = probe(feats)
     pred = MF.interpolate(pred, size=target.shape[-2:], mode="bilinear")
     loss = MF.bce_loss(pred, target)
+    MF.backward(loss)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach()
+
+
+def train_taskonomy_step(model, probe, optimizer, scheduler, images, target, valid, detach_model=True, feats=None):
+    """One iteration of Taskonomy probing (the reference ships the parts, not the loop: INTEGRATION.md lists the conventions): the
+    probe's first C_t channels, C_t the target's, are resized bilinearly to the target and meet it in MaskedL1Loss under ``valid``
+    [B, 1, H, W]; the probe's other channels get a zero gradient.  Returns the loss as a device scalar.  ``feats`` as in
+    ``train_depth_step``."""
+    optimizer.zero_grad()
+    if feats is None:
+        feats = extract_features(model, images, detach_model)
+    _finish_pending(optimizer)
+    pred = probe(feats)
+    ct = target.shape[1]
+    if pred.shape[1] < ct:
+        raise ValueError(f"the probe has {pred.shape[1]} output channels, the target {ct} (probe.output_dim)")
+    pred = MF.interpolate(pred[:, :ct], size=target.shape[-2:], mode="bilinear", align_corners=False)
+    loss = MF.masked_l1_loss(pred, target, valid)
     MF.backward(loss)
     optimizer.step()
     if scheduler is not None:
