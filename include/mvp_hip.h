@@ -108,6 +108,9 @@ typedef struct {
                                 Added within 8: mvp_task_prepare, mvp_masked_l1_fwd_bwd and mvp_task_metrics (Taskonomy probing: raw target and
                                 valid mask on the device, masked L1 loss, AbsRel / threshold sums); new exports with their own tagged argument
                                 structs, no existing struct changed.
+                                Added within 8: mvp_pixel_score and mvp_pixel_score_workspace_bytes (the pixel-level baselines of the 2AFC
+                                evaluation: PSNR and SSIM of triplets with the running confusion counts); new exports with their own tagged
+                                argument struct, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -842,6 +845,53 @@ struct mvp_twoafc_args {
  * mvp_twoafc_score rejects. */
 int64_t mvp_twoafc_workspace_bytes(int B, int C, int HW);
 int mvp_twoafc_score(const mvp_twoafc_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * (added within ABI 8; new exports with their own tagged argument struct, no existing struct changed.)
+ * The pixel-level baselines of the 2AFC evaluation: PSNR and SSIM of a batch of triplets, scored and counted like mvp_twoafc_score.
+ * x in {ref, left, right} points at B images of [C, H, W] fp32, image b starting at element b * ld (the three parts of one stacked
+ * [3B, C, H, W] batch are passed as three pointers; they may alias).  Values are used as they are: nothing is clamped to [0, 1].
+ *   metric 1, SSIM (evals/utils/losses.py:203-251 of the reference, size_average=False):
+ *     g[k]   = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, rounded to fp32 and divided by their fp32 sum; window = g g^T
+ *     mu_x   = window * x,  E_xy = window * (x y)      per channel, zero padding of 5 pixels
+ *     map    = ((2 mu_1 mu_2 + C1) (2 (E_12 - mu_1 mu_2) + C2)) / ((mu_1^2 + mu_2^2 + C1) ((E_11 - mu_1^2) + (E_22 - mu_2^2) + C2))
+ *              with C1 = 1e-4, C2 = 9e-4;   score = mean of map over C * H * W.   Any H, W >= 1.
+ *   metric 0, PSNR:  mse = mean over C * H * W of (a - b)^2,  score = 10 log10(1 / mse): the peak is 1; mse = 0 gives +inf.
+ *     sim[b] = {score(ref, left), score(ref, right)},   pred[b] = sim[b][0] > sim[b][1] ? 0 : 1   (compared as written, in fp32; NaN
+ *     gives 1, two +inf give 1);   counts = TP, FP, FN, TN of pred against label with positive = 1, as in mvp_twoafc_score: written only
+ *     when label is given, overwritten when accumulate == 0, added to otherwise.
+ * Precision.  PSNR: differences, squares and sums in fp64, one rounding to fp32: |sim - exact| <= 2^-24 max(1, |exact|).  SSIM: the window
+ * is applied separably with the fp32 weights g in fp64 arithmetic (the reference's 2-D window is g g^T rounded to fp32: 2^-24 relative
+ * per tap; on the score <= 3e-8 for noise and <= 2e-7 for smooth images, where torch's own fp32 error is 1e-5), the map, whose E - mu^2 cancels against C2, and every sum in fp64, one rounding to fp32.  Both scores of
+ * a triplet come from the same instruction sequence: bitwise-equal left and right give bitwise-equal scores, hence pred = 1; a
+ * candidate bitwise equal to the reference image gives SSIM 1.0f exactly and PSNR +inf.  A NaN in left does not reach sim[b][1].
+ * How: the three images are read once.  SSIM: a grid over (triplet, channel, 16 x 32 tile); the tile with a 5-pixel zero-filled halo
+ * in LDS, eight filtered planes (r, l, q, r^2, l^2, q^2, r l, r q: the reference image's serve both pairs), two fp64 partials per
+ * workgroup.  PSNR: a grid over (triplet, chunk of >= 4096 elements), 16-byte loads when ld % 4 == 0 and the bases are 16-byte aligned.
+ * One wave per triplet folds the partials in a fixed order.  No floating-point atomics (the counts are integers), no sync, no
+ * allocation; two calls give the same bits.  Elements C * H * W .. ld - 1 of an image are never read.
+ * MVP_EINVAL: NULL ref / left / right / sim / pred; counts without label; B, C, H or W <= 0; C * H * W > 2^31 - 1; ld < C * H * W;
+ * metric not 0 or 1; B * (partials per triplet) > 2^31 - 1; workspace NULL, not 8-byte aligned or shorter than
+ * mvp_pixel_score_workspace_bytes(B, C, H, W, metric); counts not 8-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_pixel_score_args mvp_pixel_score_args;
+struct mvp_pixel_score_args {
+  const float* ref; const float* left; const float* right; /* image b of each at element b * ld, [C, H, W] fp32              */
+  const float* label;                                      /* optional [B] fp32, exactly 0 or 1                              */
+  float* sim;                                              /* [B, 2]  score(ref, left), score(ref, right)                    */
+  int32_t* pred;                                           /* [B]     0 = left is the closer one, 1 = right                  */
+  int64_t* counts;                                         /* optional [4] TP, FP, FN, TN; needs label                       */
+  void* workspace; int64_t workspace_bytes;                /* >= mvp_pixel_score_workspace_bytes(...), 8-byte aligned        */
+  int64_t ld;                                              /* elements between consecutive images, >= C * H * W              */
+  int B, C, H, W;
+  int metric;                                              /* 0 = PSNR, 1 = SSIM                                             */
+  int accumulate;                                          /* != 0: add to counts instead of overwriting them                */
+};
+/* Workspace: 16 bytes per workgroup of the first pass.  SSIM: B * C * ceil(H / 16) * ceil(W / 32) of them; PSNR: B * chunks, chunks =
+ * ceil(C H W / e) with e the smallest of 4096, 8192, ... that gives at most 1024.  0 for sizes (or a metric) that mvp_pixel_score
+ * rejects. */
+int64_t mvp_pixel_score_workspace_bytes(int B, int C, int H, int W, int metric);
+int mvp_pixel_score(const mvp_pixel_score_args*, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * (added within ABI 8; new exports with their own tagged argument structs, no existing struct changed.)

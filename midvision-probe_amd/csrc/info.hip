@@ -35,7 +35,7 @@ extern "C" int mvp_sizeof(const char* name) {
   MVP_SZ(mvp_gemm_scaled_args) MVP_SZ(mvp_patch_gather_ld_args) MVP_SZ(mvp_prefix_rows_args) MVP_SZ(mvp_gemm_route_t) MVP_SZ(mvp_rope2d_qkv_args) MVP_SZ(mvp_attention_bias_args)
   MVP_SZ(mvp_gather_rows_args) MVP_SZ(mvp_relpos_terms_args) MVP_SZ(mvp_attention_relpos_args) MVP_SZ(mvp_knn_ratio_args)
   MVP_SZ(mvp_bn_act_args) MVP_SZ(mvp_bce_loss_args) MVP_SZ(mvp_binary_counts_args) MVP_SZ(mvp_pointcloud_sample_args)
-  MVP_SZ(mvp_twoafc_args)
+  MVP_SZ(mvp_twoafc_args) MVP_SZ(mvp_pixel_score_args)
   MVP_SZ(mvp_ncut_affinity_args) MVP_SZ(mvp_ncut_threshold_args) MVP_SZ(mvp_ncut_fiedler_args) MVP_SZ(mvp_ncut_partition_args)
   MVP_SZ(mvp_dwconv7_ln_args) MVP_SZ(mvp_grn_args)
   MVP_SZ(mvp_crf_filter_args) MVP_SZ(mvp_crf_update_args) MVP_SZ(mvp_mask_finish_args)

@@ -10,6 +10,7 @@ from .dino import DINO  # noqa: F401
 from .ibot import iBOT  # noqa: F401
 from .mae import MAE  # noqa: F401
 from .mocov3 import MoCoV3  # noqa: F401
+from .pixel_metrics import PSNR, SSIM  # noqa: F401
 from .sam import SAM  # noqa: F401
 from .siglip import SigLIP  # noqa: F401
 from . import ssl_resnet50 as _ssl  # noqa: E402

@@ -200,6 +200,12 @@ class TwoafcArgs(Struct, c_name="mvp_twoafc_args"):  # pooled cosine scoring of 
                 ("workspace", _vp), ("workspace_bytes", _i64), ("ld", _i64), ("B", _i), ("C", _i), ("HW", _i), ("accumulate", _i)]
 
 
+class PixelScoreArgs(Struct, c_name="mvp_pixel_score_args"):  # PSNR / SSIM scoring of 2AFC triplets + running confusion counts (added within ABI 8)
+    _fields_ = [("ref", _vp), ("left", _vp), ("right", _vp), ("label", _vp), ("sim", _vp), ("pred", _vp), ("counts", _vp),
+                ("workspace", _vp), ("workspace_bytes", _i64), ("ld", _i64), ("B", _i), ("C", _i), ("H", _i), ("W", _i), ("metric", _i),
+                ("accumulate", _i)]
+
+
 class NcutAffinityArgs(Struct, c_name="mvp_ncut_affinity_args"):  # MaskCut: normalised, painted-out patch affinity (added within ABI 8)
     _fields_ = [("feats", _vp), ("painted", _vp), ("active", _vp), ("A", _vp), ("sums", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
                 ("ldf", _i64), ("Bimg", _i), ("C", _i), ("N", _i)]
@@ -428,6 +434,8 @@ SYMBOLS = {
     "mvp_pointcloud_sample": PointcloudSampleArgs,
     "mvp_twoafc_score": TwoafcArgs,
     "mvp_twoafc_workspace_bytes": None,
+    "mvp_pixel_score": PixelScoreArgs,
+    "mvp_pixel_score_workspace_bytes": None,
     "mvp_ncut_workspace_bytes": None,
     "mvp_ncut_affinity": NcutAffinityArgs,
     "mvp_ncut_threshold": NcutThresholdArgs,
@@ -466,6 +474,7 @@ SIGNATURES = {
     "mvp_gemm_tn_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "mvp_knn_workspace_bytes": (_i64, [_i, _i, _i]),
     "mvp_twoafc_workspace_bytes": (_i64, [_i, _i, _i]),
+    "mvp_pixel_score_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "mvp_ncut_workspace_bytes": (_i64, [_i, _i]),
     "mvp_grn_workspace_bytes": (_i64, [_i, _i, _i]),
     "mvp_augment_partials_bytes": (_i64, [_i]),

@@ -521,6 +521,23 @@ def twoafc_score(ref, left, right, sim, pred, workspace, B, Cdim, HW, ld, label=
     _traced("hbm", "twoafc_score", 0, float(3 * B * Cdim * HW * 4), lambda: lib.call("mvp_twoafc_score", a))
 
 
+PIXEL_METRICS = {"psnr": 0, "ssim": 1}  # mvp_pixel_score_args.metric
+
+
+def pixel_score_workspace_bytes(B: int, Cdim: int, H: int, W: int, metric: str) -> int:
+    return int(lib.load().mvp_pixel_score_workspace_bytes(B, Cdim, H, W, PIXEL_METRICS[metric]))
+
+
+def pixel_score(ref, left, right, sim, pred, workspace, B, Cdim, H, W, ld, metric, label=None, counts=None, accumulate=False) -> None:
+    """sim [B, 2] / pred [B] int32 of B triplets of [C, H, W] fp32 images ld elements apart under ``metric`` ("psnr": 10 log10(1 / mse),
+    peak 1; "ssim": the reference's 11 x 11 Gaussian SSIM), and (with label [B]) the TP / FP / FN / TN in counts [4] int64, overwritten or
+    added to (include/mvp_hip.h: mvp_pixel_score).  ref / left / right may be slices of one tensor."""
+    a = lib.PixelScoreArgs(lib.ptr(ref), lib.ptr(left), lib.ptr(right), lib.ptr(label), lib.ptr(sim), lib.ptr(pred), lib.ptr(counts),
+                           lib.ptr(workspace), workspace.numel() * workspace.element_size(), ld, B, Cdim, H, W, PIXEL_METRICS[metric],
+                           int(accumulate))
+    _traced("hbm", "pixel_score", 0, float(3 * B * Cdim * H * W * 4), lambda: lib.call("mvp_pixel_score", a))
+
+
 def bn_act_workspace(device) -> torch.Tensor:
     """A workspace for bn_act_fwd / bn_act_bwd (MVP_BN_ACT_WORKSPACE_BYTES of fp64 partials)."""
     return torch.empty(lib.BN_ACT_WORKSPACE_BYTES // 8, dtype=torch.float64, device=device)

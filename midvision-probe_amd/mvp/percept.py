@@ -7,6 +7,7 @@ forward (class tokens as they are, CNN maps with the global average pool fused i
 confusion counts on the device: one device-to-host transfer per shard, after the loop."""
 from __future__ import annotations
 
+import functools
 from typing import Dict, Sequence, Tuple
 
 import torch
@@ -43,6 +44,31 @@ def score_triplets(ref: torch.Tensor, left: torch.Tensor, right: torch.Tensor, l
     pred = torch.empty(B, dtype=torch.int32, device=dev) if pred is None else pred
     ws = torch.empty(max(1, ops.twoafc_workspace_bytes(B, Cdim, HW) // 8), dtype=torch.float64, device=dev)
     ops.twoafc_score(ref, left, right, sim, pred, ws, B, Cdim, HW, ld, label=label, counts=counts, accumulate=accumulate)
+    return sim, pred
+
+
+def score_pixel_triplets(ref: torch.Tensor, left: torch.Tensor, right: torch.Tensor, metric: str, label=None, counts=None,
+                          accumulate=False, pred=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """score_triplets for the pixel-level baselines: -> (sim [B, 2] fp32, pred [B] int32) of B triplets of IMAGES under ``metric``
+    ("psnr": 10 log10(1 / mse), peak 1; "ssim": the reference's 11 x 11 Gaussian SSIM, per image).  ref / left / right: fp32 device
+    tensors [B, C, H, W], each contiguous per image with the same stride between images (slices of one stacked batch are taken as they
+    are); values are used as they are, nothing is clamped.  label / counts / accumulate / pred as in score_triplets."""
+    if metric not in ops.PIXEL_METRICS:
+        raise ValueError(f"score_pixel_triplets: metric {metric!r}; one of {sorted(ops.PIXEL_METRICS)}")
+    for t in (ref, left, right):
+        if not t.is_cuda:
+            raise lib.MvpError("score_pixel_triplets needs device tensors (no CPU fallback)")
+        if t.dtype != torch.float32 or t.shape != ref.shape or t.dim() != 4 or t.stride() != ref.stride():
+            raise ValueError(f"score_pixel_triplets: three fp32 tensors of one shape [B, C, H, W], got {tuple(t.shape)} {t.dtype}")
+    B, Cdim, H, W = ref.shape
+    if not ref[0].is_contiguous():  # (equal strides: this holds for left and right too)
+        raise ValueError("score_pixel_triplets: every image must be contiguous")
+    ld = ref.stride(0) if B > 1 else Cdim * H * W
+    dev = ref.device
+    sim = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    pred = torch.empty(B, dtype=torch.int32, device=dev) if pred is None else pred
+    ws = torch.empty(max(1, ops.pixel_score_workspace_bytes(B, Cdim, H, W, metric) // 8), dtype=torch.float64, device=dev)
+    ops.pixel_score(ref, left, right, sim, pred, ws, B, Cdim, H, W, ld, metric, label=label, counts=counts, accumulate=accumulate)
     return sim, pred
 
 
@@ -153,6 +179,8 @@ def predict_batch(model, dataloader, output_dir, wandb_use=False, rank: int = 0,
     """Reference: evaluate_model_percepture.py:67-167 -> (results, metrics, errors); results = [{"id", "gt", "prediction"}] in loader
     order.  ``output_dir`` and ``wandb_use`` are accepted and unused (the reference's csv dump is commented out; no wandb here).
     With world > 1 every rank returns the merged result of all ranks."""
+    if not torch.cuda.is_available():
+        raise lib.MvpError("predict_batch needs a GPU: the evaluation runs on the device (no CPU fallback)")
     dev = torch.device("cuda", torch.cuda.current_device())
     model = model.to(dev)
     model.eval()
@@ -187,10 +215,13 @@ def predict_batch(model, dataloader, output_dir, wandb_use=False, rank: int = 0,
         _check_labels(gts, f"batch {bi}")  # sklearn rejects them too; here they would silently fall out of the counts
         images = ring.to_device((img_ref, img_left, img_right), dev).flatten(0, 1)  # [3B, 3, H, W]: ref | left | right
         label = ring.to_device((torch.as_tensor(p).reshape(-1),), dev)[0]
-        with torch.no_grad():
-            feats = _triplet_features(model, model(images))
+        if getattr(model, "arch", None) == "metric":  # PSNR / SSIM (evals/models/pixel_metrics.py): no forward, the images are scored
+            feats, score = images, functools.partial(score_pixel_triplets, metric=model.metric)
+        else:
+            with torch.no_grad():
+                feats, score = _triplet_features(model, model(images)), score_triplets
         pred, counts = log.reserve(B)
-        score_triplets(feats[:B], feats[B:2 * B], feats[2 * B:], label=label, counts=counts, accumulate=True, pred=pred)
+        score(feats[:B], feats[B:2 * B], feats[2 * B:], label=label, counts=counts, accumulate=True, pred=pred)
         rows.append((bi, id_list, gts))
     counts, preds = log.fetch()
     out_rows, k = [], 0
@@ -206,16 +237,34 @@ class SyntheticTwoAFC(torch.utils.data.Dataset):
     """2AFC-shaped triplets with the item contract of evals/datasets/twoafcdataset.py:46-58: (img_ref, img_left, img_right, p, id),
     images [3, H, W] fp32, p float32 0 / 1, id an int.  One of left / right is the reference image plus small noise, the other an
     independent image; p = 1 when the LEFT one is the independent (far) image, i.e. p is the label of the closer side as the
-    evaluation predicts it (0 = left closer, 1 = right closer).  Item i depends on (seed, i) alone."""
+    evaluation predicts it (0 = left closer, 1 = right closer).  Item i depends on (seed, i) alone.
+
+    ``preprocess``: "DEFAULT" gives unnormalised Gaussian images, what a backbone's normalised input looks like.  "SSIM" / "PSNR" (the
+    model types of the reference's get_preprocess whose transform is ToTensor() alone) give what a decoded 8-bit image looks like:
+    values k / 255 in [0, 1].  The reference image is a smooth field (a bilinearly enlarged 4 x 4 grid in [0.25, 0.75]) plus noise of
+    0.08, the near image the reference plus ``noise`` x Gaussian noise, clamped and quantised again, the far image an independent
+    image of the same kind."""
 
     name = "synthetic_twoafc"
 
-    def __init__(self, num_triplets=64, image_size=224, seed=0, noise=0.05, split="test"):
-        self.n, self.seed, self.noise, self.split = int(num_triplets), int(seed), float(noise), split
+    def __init__(self, num_triplets=64, image_size=224, seed=0, noise=0.05, split="test", preprocess="DEFAULT"):
+        if preprocess not in ("DEFAULT", "SSIM", "PSNR"):
+            raise ValueError(f"SyntheticTwoAFC: preprocess {preprocess!r}; one of DEFAULT, SSIM, PSNR")
+        self.n, self.seed, self.noise, self.split, self.preprocess = int(num_triplets), int(seed), float(noise), split, preprocess
         self.size = (int(image_size), int(image_size)) if isinstance(image_size, int) else tuple(int(v) for v in image_size)
 
     def __len__(self):
         return self.n
+
+    @staticmethod
+    def _natural(g, H, W):
+        coarse = torch.rand(1, 3, 4, 4, generator=g)
+        field = torch.nn.functional.interpolate(coarse, size=(H, W), mode="bilinear", align_corners=True)[0]
+        return 0.25 + 0.5 * field + 0.08 * torch.randn(3, H, W, generator=g)
+
+    @staticmethod
+    def _eight_bit(x):
+        return (x.clamp(0.0, 1.0) * 255.0).round() / 255.0
 
     def __getitem__(self, i):
         import numpy as np
@@ -224,9 +273,14 @@ class SyntheticTwoAFC(torch.utils.data.Dataset):
             raise IndexError(i)
         g = torch.Generator().manual_seed(self.seed * 7919 + int(i))
         H, W = self.size
-        ref = torch.randn(3, H, W, generator=g)
-        near = ref + self.noise * torch.randn(3, H, W, generator=g)
-        far = torch.randn(3, H, W, generator=g)
+        if self.preprocess == "DEFAULT":
+            ref = torch.randn(3, H, W, generator=g)
+            near = ref + self.noise * torch.randn(3, H, W, generator=g)
+            far = torch.randn(3, H, W, generator=g)
+        else:
+            ref = self._eight_bit(self._natural(g, H, W))
+            near = self._eight_bit(ref + self.noise * torch.randn(3, H, W, generator=g))
+            far = self._eight_bit(self._natural(g, H, W))
         p = int(torch.randint(0, 2, (1,), generator=g))
         left, right = (far, near) if p == 1 else (near, far)
         return ref, left, right, np.float32(p), int(i)
