@@ -47,7 +47,13 @@ extern "C" {
                              BF16X3 (tests/test_gpu_kernels.py measures it against fp64, with the ViT goldens' feature error) at 2/3 of its
                              matrix-pipe work, on a chip whose clock is held down by exactly that work (the large-M kernel: -19 % time).
                              Range: |a| <= 65504 (hi and lo saturate there; beyond it the result is wrong, not NaN); values whose lo half falls
-                             below fp16's normal range (|a| < 5e-4, |w| < 5e-4) keep absolute, not relative, precision.                     */
+                             below fp16's normal range (|a| < 5e-4, |w| < 5e-4) keep absolute, not relative, precision.
+                             The ViT wrappers run this mode unless told otherwise (mvp/backbone.py default_precision(); MVP_PREC_BF16X3 is what a bare
+                             engine, the ResNet / ConvNeXt trunks and the probes run).  Because saturation is silent, the wrappers carry a range
+                             guard (range_guard= / MVP_F16_GUARD: off | auto | warn | raise | fallback): one audited forward in which
+                             mvp_f16_range_scan reads every fp16-form operand right before its consumer; a saturated or non-finite half
+                             warns, raises, or rebuilds the engine in MVP_PREC_BF16X3.  `auto` (the default) arms it for weights read from a
+                             checkpoint file only.                                                                                            */
 
 #define MVP_ACT_NONE 0
 #define MVP_ACT_GELU 1 /* exact erf GELU (torch nn.GELU default)            */
@@ -111,6 +117,9 @@ typedef struct {
                                 Added within 8: mvp_pixel_score and mvp_pixel_score_workspace_bytes (the pixel-level baselines of the 2AFC
                                 evaluation: PSNR and SSIM of triplets with the running confusion counts); new exports with their own tagged
                                 argument struct, no existing struct changed.
+                                Added within 8: mvp_f16_range_scan (one read-only pass over the fp16 hi half of a pair operand into a 16-byte
+                                record of maximum / saturated / non-finite / scanned counts: the range guard under MVP_PREC_F16X2); a new export
+                                with its own tagged argument struct, no existing struct changed.
                              7: mvp_bn_running_update_n (a new export); mvp_gemm_args.out_f16_col0 < -1 and MVP_ATT_V_F16_QK_F16 (new values of existing fields); every struct as in 6.
                                 Later additions within 7 (new exports with their own argument structs; no existing struct changed):
                                 mvp_gemm_scaled (LayerScale epilogue), mvp_patch_gather_ld (padded patch rows), mvp_prefix_rows (CLS + register rows);
@@ -1438,6 +1447,34 @@ struct mvp_task_metrics_args {
   float t1, t2, t3;
 };
 int mvp_task_metrics(const mvp_task_metrics_args*, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Range scan of an fp16-form pair operand (added within ABI 8; a new export with its own tagged argument struct, no existing struct
+ * changed).  No reference counterpart: the reference computes in fp32.  Under MVP_PREC_F16X2 the kernels that write activation pairs and
+ * Q / K (LayerNorm, attention, the GEMM epilogues, mvp_swiglu_fwd, mvp_rope2d_qkv, mvp_relpos_terms) saturate the hi half at +-65504
+ * instead of overflowing, so an operand that left fp16's range gives a finite, wrong result.  This pass reads the hi halves of
+ * columns [col0, col0 + cols) of `rows` rows, 16 bytes per lane, at read rate, and writes nothing but the record:
+ *   record[0]  max over the scanned elements of bits & 0x7FFF  (atomic max: the fp16 magnitude order; NaN > inf > 65504)
+ *   record[1] += number with bits & 0x7FFF == 0x7BFF           (|v| = 65504: saturated, or exactly representable — not told apart)
+ *   record[2] += number with bits & 0x7FFF >= 0x7C00           (inf or NaN)
+ *   record[3] += number scanned, mod 2^32                      (rows * cols per call)
+ * The caller zeroes the record; calls accumulate into it (several operands, or several launches, may share one).  Only hi is read: lo
+ * may be bf16 (the V third of qkv) and cannot saturate unless hi did.  Words outside the window — the gap up to ld, the lo blocks of
+ * the interleaved layout — are never loaded.  One atomic max and up to three atomic adds on unsigned per workgroup (an add of zero is
+ * left out), at most 256 workgroups: integer max and add commute, so the record is bit-reproducible.
+ * MVP_EINVAL before any launch: a NULL pointer, rows < 1, cols < 8, col0 < 0, col0 / cols / ld not multiples of 8, hi not 16-byte or
+ * record not 4-byte aligned, a window that ends beyond ld, an unknown layout, rows * cols / 8 >= 2^31.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mvp_f16_scan_args mvp_f16_scan_args;
+struct mvp_f16_scan_args {
+  const mvp_bf16* hi;  /* MVP_PAIR_SEPARATE: the hi array [rows, ld]; MVP_PAIR_A_ILV32: the one array, hi | lo interleaved per 32 columns */
+  uint32_t* record;    /* 4 words on the device, accumulated into                                                                        */
+  int rows;
+  int col0, cols;      /* the window of pair columns, each % 8 == 0                                                                      */
+  int ld;              /* row stride of the STORED array in 16-bit words, % 8 == 0 (MVP_PAIR_A_ILV32: twice the pair's column count)      */
+  int layout;          /* MVP_PAIR_SEPARATE or MVP_PAIR_A_ILV32                                                                          */
+};
+int mvp_f16_range_scan(const mvp_f16_scan_args*, void* stream);
 
 #ifdef __cplusplus
 }

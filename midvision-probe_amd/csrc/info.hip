@@ -42,6 +42,7 @@ extern "C" int mvp_sizeof(const char* name) {
   MVP_SZ(mvp_augment_stats_args) MVP_SZ(mvp_augment_apply_args)
   MVP_SZ(mvp_swiglu_args)
   MVP_SZ(mvp_task_prepare_args) MVP_SZ(mvp_masked_l1_args) MVP_SZ(mvp_task_metrics_args)
+  MVP_SZ(mvp_f16_scan_args)
 #undef MVP_SZ
   return -1;
 }

@@ -33,7 +33,7 @@ class BEiTV2(bb.ViTBackbone):
     replay_after_norm = True
 
     def __init__(self, model_name="beit_vitb16", layer=-1, arch="beit_vitb16", output="dense", return_multilayer=False, add_norm=False,
-                 return_kqv=False, fixed_size=224, mode_selected="k", return_cls=False, weights=None, img_size=None, precision=None, init_seed=0):
+                 return_kqv=False, fixed_size=224, mode_selected="k", return_cls=False, weights=None, img_size=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         self.arch = "vit"
         self.return_cls = return_cls
@@ -47,6 +47,7 @@ class BEiTV2(bb.ViTBackbone):
         if sd is None:
             path = bb.find_checkpoint(bb.BEIT_CKPT_FILE)
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = bb.load_checkpoint_file(path)
             else:
                 warnings.warn(f"no local checkpoint {bb.BEIT_CKPT_FILE}: using seeded random init (seed={init_seed})")
@@ -69,6 +70,7 @@ class BEiTV2(bb.ViTBackbone):
         self.batchnorms = nn.ModuleList([nn.BatchNorm1d(C) for _ in self.multilayers])
         self.return_kqv, self.fixed_size, self.mode_selected = return_kqv, fixed_size, mode_selected
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
     def supports_grouping(self) -> bool:
         return not (len(self.multilayers) == 1 and self.return_cls)
@@ -78,10 +80,15 @@ class BEiTV2(bb.ViTBackbone):
             return None, 2
         return super()._tap_bn()
 
-    def forward(self, images):
+    def _engine_images(self, images):
+        """The resize to the model's image size that ``forward`` starts with (also what the f16x2 range guard audits)."""
         if tuple(images.shape[-2:]) != self.img_size:  # (a same-size bilinear resize with align_corners=False returns its input's values)
             with torch.no_grad():
                 images = MF.interpolate(images, size=self.img_size, mode="bilinear", align_corners=False)  # beit_v2.py:255-257
+        return images
+
+    def forward(self, images):
+        images = self._engine_images(images)
         single_cls = len(self.multilayers) == 1 and self.return_cls
         taps = self._extract(images, want_cls=single_cls)
         if isinstance(taps, bb.TapGroups):  # several batches stacked into one forward (mvp/pipeline.py): one result per batch

@@ -21,7 +21,7 @@ class CLIP(bb.ViTBackbone):
     ln_eps = 1e-5
 
     def __init__(self, arch="ViT-B-16", checkpoint="openai", output="dense", layer=-1, return_multilayer=False, add_norm=False,
-                 weights=None, precision=None, init_seed=0):
+                 weights=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         assert output in ["dense-cls", "cls", "gap", "dense"]
         if arch not in bb.CLIP_ARCH:
@@ -34,6 +34,7 @@ class CLIP(bb.ViTBackbone):
         if sd is None:
             path = bb.find_checkpoint(self.checkpoint_name)
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = bb.load_checkpoint_file(path)
             else:
                 warnings.warn(f"no local checkpoint for {self.checkpoint_name}: using seeded random init (seed={init_seed})")
@@ -50,6 +51,7 @@ class CLIP(bb.ViTBackbone):
         self.feat_dim = [feat_dim] * 4
         self.batchnorms = nn.ModuleList([nn.BatchNorm1d(self.vit.embed_dim) for _ in self.multilayers])
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
     def forward(self, images):
         return self._finish(self._extract(images))

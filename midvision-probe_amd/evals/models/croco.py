@@ -40,7 +40,7 @@ class CROCO(bb.ViTBackbone):
     pos_embed_mode = "fixed"
 
     def __init__(self, model_name="vitb16", layer=-1, output="dense", return_multilayer=False, add_norm=False, return_kqv=False,
-                 fixed_size=480, mode_selected="k", return_layers=None, return_cls=False, weights=None, precision=None, init_seed=0):
+                 fixed_size=480, mode_selected="k", return_layers=None, return_cls=False, weights=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         self.arch = "vit"
         self.return_cls = return_cls
@@ -51,6 +51,7 @@ class CROCO(bb.ViTBackbone):
         if sd is None:
             path = bb.find_checkpoint(bb.CROCO_CKPT_FILES[self.ckpt_key])
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = _load_published(path)
             else:
                 warnings.warn(f"no local checkpoint {bb.CROCO_CKPT_FILES[self.ckpt_key]}: using seeded random init (seed={init_seed})")
@@ -79,11 +80,17 @@ class CROCO(bb.ViTBackbone):
         self.batchnorms = nn.ModuleList([nn.BatchNorm1d(C) for _ in self.multilayers])
         self.return_kqv, self.fixed_size, self.mode_selected = return_kqv, fixed_size, mode_selected
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
-    def forward(self, images):
+    def _engine_images(self, images):
+        """The resize to the model's image size that ``forward`` starts with (also what the f16x2 range guard audits)."""
         if tuple(images.shape[-2:]) != self.img_size:  # (a same-size bilinear resize with align_corners=False returns its input's values)
             with torch.no_grad():
                 images = MF.interpolate(images, size=self.img_size, mode="bilinear", align_corners=False)  # croco.py:138-140
+        return images
+
+    def forward(self, images):
+        images = self._engine_images(images)
         taps = self._extract(images)
         if isinstance(taps, bb.TapGroups):  # several batches stacked into one forward (mvp/pipeline.py): one result per batch
             return pipeline.GroupedFeatures((t[0] if len(t) == 1 else t) for t in taps)

@@ -16,7 +16,7 @@ DINO_ARCH = {"vitb16": ("dino_vitbase16_pretrain", 16), "vitb8": ("dino_vitbase8
 class DINO(bb.ViTBackbone):
     def __init__(self, dino_name="dino", model_name="vitb16", output="dense", layer=-1, return_multilayer=False, add_norm=False,
                  return_kqv=False, fixed_size=480, mode_selected="k", return_layers=None, return_cls=False,
-                 weights=None, precision=None, init_seed=0):
+                 weights=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         feat_dims = {"vitb8": 768, "vitb16": 768, "vitb14": 768, "vitb14_reg": 768, "vitl14": 1024, "vitg14": 1536}
         v2 = dino_name == "dinov2"
@@ -39,6 +39,7 @@ class DINO(bb.ViTBackbone):
             hub = bb.DINOV2_HUB_NAMES[model_name] if v2 else DINO_ARCH[model_name][0]
             path = bb.find_checkpoint(self.checkpoint_name, hub)
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = bb.load_checkpoint_file(path)
             elif v2 and bb.DINOV2_FFN.get(model_name) == "swiglu":
                 # 4.4 GB of random weights in place of a missing file is never what was meant
@@ -71,6 +72,7 @@ class DINO(bb.ViTBackbone):
         self.heads, self.ln_eps = self.vit.embed_dim // 64, 1e-6
         self.pos_embed_mode = "dinov2_reg" if (v2 and self.has_registers) else "dino"
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
     def forward(self, images):
         if self.return_kqv:  # dino.py:164-169

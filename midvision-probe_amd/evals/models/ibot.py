@@ -11,7 +11,7 @@ from mvp import backbone as bb
 
 class iBOT(bb.ViTBackbone):
     def __init__(self, model_type="base", output="dense", layer=-1, return_multilayer=False, add_norm=False, return_kqv=False,
-                 fixed_size=480, mode_selected="k", return_cls=False, weights=None, precision=None, init_seed=0):
+                 fixed_size=480, mode_selected="k", return_cls=False, weights=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         self.arch = "vit"
         self.return_cls = return_cls
@@ -28,6 +28,7 @@ class iBOT(bb.ViTBackbone):
         if sd is None:  # reference: urlretrieve + torch.load(...)["state_dict"] (ibot.py:46-56)
             path = bb.find_checkpoint(ckpt_name)
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = {k.replace("module.", ""): v for k, v in bb.load_checkpoint_file(path).items()}
                 sd = {k: v for k, v in sd.items() if not k.startswith("head.")}
             else:
@@ -42,12 +43,14 @@ class iBOT(bb.ViTBackbone):
         self.return_kqv, self.fixed_size, self.mode_selected = return_kqv, fixed_size, mode_selected
         self.heads, self.ln_eps, self.pos_embed_mode = self.vit.embed_dim // 64, 1e-6, "dino"
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
     def forward(self, images):
         if self.return_kqv:  # ibot.py:182-186
             return self.extract_kqv(self.preprocess_image(images)[0])
         if len(self.multilayers) == 1 and self.return_cls:
             # ibot.py:199-200: raw CLS token of the tapped block (no BN, no later blocks)
+            self._guard(images)  # (this shortcut does not pass through _extract)
             eng = self.engine()
             with torch.no_grad():
                 return eng.forward_tokens(images, self.multilayers[0] + 1)[:, 0]

@@ -15,7 +15,7 @@ class MAE(bb.ViTBackbone):
     tap_input_of_block = True
 
     def __init__(self, checkpoint="facebook/vit-mae-base", output="dense", layer=-1, return_multilayer=False, add_norm=False,
-                 return_kqv=False, fixed_size=480, mode_selected="k", return_cls=False, weights=None, precision=None, init_seed=0):
+                 return_kqv=False, fixed_size=480, mode_selected="k", return_cls=False, weights=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         self.arch = "vit"
         self.return_cls = return_cls
@@ -28,6 +28,7 @@ class MAE(bb.ViTBackbone):
         if sd is None:  # reference: ViTMAEForPreTraining.from_pretrained(checkpoint).vit (mae.py:33)
             path = bb.find_checkpoint(checkpoint.split("/")[1], "vit-mae-base")
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = bb.load_checkpoint_file(path)
             else:
                 warnings.warn(f"no local checkpoint for {checkpoint}: using seeded random init (seed={init_seed})")
@@ -45,6 +46,7 @@ class MAE(bb.ViTBackbone):
         self.return_kqv, self.fixed_size, self.mode_selected = return_kqv, fixed_size, mode_selected
         self.heads, self.ln_eps, self.pos_embed_mode = self.vit.embed_dim // 64, 1e-12, "fixed"
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
     def resize_pos_embed(self, image_size):
         """mae.py:74-89: rebuild the 2-D sincos table for the new grid."""
@@ -57,9 +59,16 @@ class MAE(bb.ViTBackbone):
         dev = self.vit.pos_embed.device
         self.vit.pos_embed = nn.Parameter(torch.from_numpy(pe).float().unsqueeze(0).to(dev), requires_grad=False)
 
-    def forward(self, images):
+    def _engine_images(self, images):
+        """``forward``'s first step: the sincos table rebuilt for the batch's size (the images pass through; also run by the f16x2
+        range guard, which must audit the engine this size runs on)."""
         if tuple(self.image_size) != tuple(images.shape[-2:]):
             self.resize_pos_embed(images.shape[-2:])
+        return images
+
+    def forward(self, images):
+        images = self._engine_images(images)
         if len(self.multilayers) == 1 and self.return_cls:
+            self._guard(images)  # (this shortcut does not pass through _extract)
             return self.engine().forward_tokens(images, self.multilayers[0])[:, 0]
         return self._finish(self._extract(images))

@@ -27,7 +27,7 @@ class SAM(bb.ViTBackbone):
     ln_eps = 1e-6
     pos_embed_mode = "sam"
 
-    def __init__(self, arch, output="dense", layer=-1, return_multilayer=False, add_norm=False, weights=None, precision=None, init_seed=0):
+    def __init__(self, arch, output="dense", layer=-1, return_multilayer=False, add_norm=False, weights=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         assert output in ["gap", "dense"], "Options: [gap, dense]"
         if add_norm:
@@ -41,6 +41,7 @@ class SAM(bb.ViTBackbone):
         if sd is None:
             path = bb.find_checkpoint(ckpt_file)
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = bb.load_checkpoint_file(path)
             else:
                 warnings.warn(f"no local checkpoint {ckpt_file}: using seeded random init (seed={init_seed})")
@@ -61,6 +62,7 @@ class SAM(bb.ViTBackbone):
         self._setup_taps(feat_dim, layer, return_multilayer, add_norm, self.vit.depth)
         self.batchnorms = nn.ModuleList([nn.BatchNorm2d(feat_dim) for _ in self.multilayers])
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
     def forward(self, x):
         _, _, h, w = x.shape

@@ -23,7 +23,7 @@ class SigLIP(bb.ViTBackbone):
     ln_eps = 1e-6
 
     def __init__(self, checkpoint="vit_large_patch16_siglip_384", output="dense", layer=-1, resize_pos_embeds=True, pretrained=True,
-                 return_multilayer=False, add_norm=False, act="gelu_tanh", weights=None, precision=None, init_seed=0):
+                 return_multilayer=False, add_norm=False, act="gelu_tanh", weights=None, precision=None, range_guard=None, init_seed=0):
         super().__init__()
         assert output in ["gap", "dense"], "Options: [gap, dense]"
         if checkpoint not in bb.SIGLIP_ARCH:
@@ -40,6 +40,7 @@ class SigLIP(bb.ViTBackbone):
         if sd is None:
             path = bb.find_checkpoint(checkpoint)
             if path is not None:
+                self.weights_from_file = True  # arms the f16x2 range guard under 'auto' (mvp/backbone.py)
                 sd = bb.load_checkpoint_file(path)
             else:
                 warnings.warn(f"no local checkpoint for {checkpoint}: using seeded random init (seed={init_seed})")
@@ -53,6 +54,7 @@ class SigLIP(bb.ViTBackbone):
         self._setup_taps(self.vit.embed_dim, layer, return_multilayer, add_norm, self.vit.depth)
         self.batchnorms = nn.ModuleList([nn.BatchNorm1d(self.vit.embed_dim) for _ in self.multilayers])
         self.set_precision(precision or bb.default_precision())
+        self.set_range_guard(range_guard)
 
     def forward(self, images):
         return self._finish(self._extract(images))

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import lib, pipeline
-from .vit import TapGroups, TapOutputs, ViTEngine, parse_precision
+from .vit import RangeAudit, TapGroups, TapOutputs, ViTEngine, parse_precision, tripped_sites
 
 
 def default_precision() -> str:
@@ -24,6 +24,25 @@ def default_precision() -> str:
     'bf16x3' (three bf16 products, fp32's exponent range) is what the ResNet trunk and the probes run either way; 'bf16' (one product)
     fails the 1e-3 feature contract."""
     return os.environ.get("MVP_PRECISION", "f16x2")
+
+
+RANGE_GUARD_MODES = ("off", "auto", "warn", "raise", "fallback")
+
+
+def range_guard_action(env: Optional[str], range_guard: Optional[str], from_file: bool, world: int) -> str:
+    """What the f16x2 range guard of a ViT wrapper does — 'off', 'warn', 'raise' or 'fallback' — from MVP_F16_GUARD (``env``; None =
+    unset = 'auto'), the wrapper's ``range_guard=`` keyword (None: the environment decides), whether its weights were read from a
+    checkpoint file (``find_checkpoint`` hit) and the number of ranks.  'auto' arms the guard for weights from a file only — never for
+    seeded random init or a ``weights=`` state dict — as 'fallback' on one rank and as 'raise' on several, so that ranks never
+    silently run different arithmetic (no collective is spent on agreeing).  'warn' / 'raise' / 'fallback' arm it whatever the source."""
+    mode = (range_guard if range_guard is not None else (env or "auto")).strip().lower()
+    if mode not in RANGE_GUARD_MODES:
+        raise ValueError(f"range guard {mode!r}: one of {', '.join(RANGE_GUARD_MODES)} (range_guard= / MVP_F16_GUARD)")
+    if mode != "auto":
+        return mode
+    if not from_file:
+        return "off"
+    return "fallback" if world <= 1 else "raise"
 
 
 def checkpoint_dir() -> str:
@@ -705,6 +724,10 @@ class ViTBackbone(nn.Module):
     rope_freq = None  # CroCo v2: RoPE<freq> on Q and K of every block (ViTEngine(rope_freq=...)); None: no rotation
     rel_pos_grid = None  # BEiT: (gh, gw) of the grid the blocks' relative-position bias tables belong to (ViTEngine(rel_pos_grid=...))
     replay_after_norm = False  # BEiT v2's wrapper: all blocks + fc_norm, then the tapped loop over the blocks again (ViTEngine.forward_taps)
+    weights_from_file = False  # set by the wrappers' loaders when ``find_checkpoint`` hit: arms the range guard under 'auto'
+    _range_guard = None  # the ``range_guard=`` keyword (None: MVP_F16_GUARD, default 'auto'); see ``range_guard_action``
+    _guard_sig = None  # the engine signature the guard was last resolved for (None: never)
+    _f16_report = None  # the last audit's table (``f16_range_report``)
     supports_pipelining = True  # per-slot buffers, tap-BN running-statistics updates deferred to the consumer (mvp/pipeline.py)
     graph_safe = True  # a pipelined forward launches only this library's kernels on fixed buffers: it can be captured in a hipGraph
 
@@ -750,6 +773,90 @@ class ViTBackbone(nn.Module):
     def set_precision(self, precision) -> None:
         self._precision = parse_precision(precision)
 
+    # ---- f16x2 range guard
+    def set_range_guard(self, range_guard: Optional[str]) -> None:
+        """``range_guard``: None (MVP_F16_GUARD decides; 'auto' when unset) or one of RANGE_GUARD_MODES.  The guard is pending again."""
+        if range_guard is not None:
+            range_guard_action(None, range_guard, False, 1)  # (validates the name)
+        self._range_guard, self._guard_sig = range_guard, None
+
+    def range_guard_action(self) -> str:
+        from . import dist
+
+        return range_guard_action(os.environ.get("MVP_F16_GUARD"), self._range_guard, bool(self.weights_from_file), dist.world_size())
+
+    def f16_range_report(self) -> Optional[List[dict]]:
+        """The per-site table of the guard's audited forward (``RangeAudit.read()``), None while no audit has run."""
+        return self._f16_report
+
+    def _engine_images(self, images: torch.Tensor) -> torch.Tensor:
+        """What ``forward(images)`` hands the engine: the wrapper's own preprocessing of a raw batch.  Here: the resize to ``fixed_size``
+        of the K / Q / V path; wrappers whose forward resizes the batch or rebuilds a position table for its size (BEiT v2, CroCo,
+        MoCo-v3, MAE) override this, and their forward calls it, so the guard audits exactly what the engine will be fed."""
+        if getattr(self, "return_kqv", False):
+            return self.preprocess_image(images)[0]
+        return images
+
+    def _guard_pending(self, images: torch.Tensor) -> Optional[str]:
+        """The guard's action ('warn' / 'raise' / 'fallback') while it is armed and still pending for the current engine signature, else
+        None.  Every call reads MVP_F16_GUARD and the world size; an armed guard also builds the engine signature (a tuple over all
+        parameters, as ``engine()`` does on every forward).  Launches nothing; a pending guard on a capturing stream raises here."""
+        action = self.range_guard_action()
+        if action == "off" or not images.is_cuda or self._guard_sig == self._signature():
+            return None
+        if torch.cuda.is_current_stream_capturing():
+            raise lib.MvpError("the f16x2 range guard is still pending and the stream is capturing: run one eager forward (or "
+                               "model.resolve_range_guard(images)) before the capture")
+        return action
+
+    def resolve_range_guard(self, images: torch.Tensor) -> None:
+        """``images``: a raw batch, as ``forward`` takes it.  While the range guard is armed and pending for the current engine signature:
+        the wrapper's own preprocessing (``_engine_images``), then ONE extra audited forward over the result (no tap BN, so no state is
+        touched) on the current stream, one synchronise of that stream, and the action — 'warn': a warning naming the first site with a
+        saturated or non-finite fp16 half; 'raise': MvpError; 'fallback': the warning, then ``set_precision('bf16x3')`` (the engine is
+        rebuilt at the next forward, as after any signature change).  The guard is resolved either way.  FeaturePipeline calls this on
+        every batch it is given (pending only on the first); ``_extract`` / ``extract_kqv`` and the single-tap class-token shortcuts call
+        ``_guard`` on the batch they are about to run.  Never inside a stream capture: a pending guard there raises before it launches
+        anything, because it would have to synchronise."""
+        action = self._guard_pending(images)
+        if action is not None:
+            self._audit_range(self._engine_images(images), action)
+
+    def _guard(self, images: torch.Tensor) -> None:
+        """``resolve_range_guard`` for a batch that is already what the engine is fed (the forward paths)."""
+        action = self._guard_pending(images)
+        if action is not None:
+            self._audit_range(images, action)
+
+    def _audit_range(self, images: torch.Tensor, action: str) -> None:
+        sig = self._signature()
+        eng = self.engine()
+        audit = RangeAudit(eng)
+        if audit.sites:
+            if images.ndim == 3:
+                images = images.unsqueeze(0)
+            with torch.no_grad():
+                eng.forward_taps(images, self.multilayers, bn=None, bn_mode=2, pack=False, tap_input_of_block=self.tap_input_of_block,
+                                 replay_after_norm=bool(self.replay_after_norm), audit=audit)
+            torch.cuda.current_stream().synchronize()
+        report = audit.read()
+        self._f16_report, self._guard_sig = report, sig
+        bad = tripped_sites(report)
+        if not bad:
+            return
+        first = bad[0]
+        top = max((r["max_abs"] for r in report), key=lambda v: float("inf") if v != v else v)
+        msg = (f"f16x2 range guard: {first['site']} holds {first['n_sat'] + first['n_nonfinite']} of {first['n_scanned']} values at or "
+               f"beyond fp16's range (|v| >= 65504; {len(bad)} of {len(report)} sites tripped, max |v| over all sites = {top})")
+        if action == "raise":
+            raise lib.MvpError(msg + ": run this model with precision='bf16x3' (MVP_PRECISION=bf16x3)")
+        if action == "fallback":
+            warnings.warn(msg + ": falling back to precision='bf16x3'")
+            self.set_precision("bf16x3")
+            self._guard_sig = self._signature()  # (a bf16x3 engine has nothing to audit)
+        else:
+            warnings.warn(msg + ": the features are wrong; run this model with precision='bf16x3' (MVP_PRECISION=bf16x3)")
+
     # ---- forward glue (dino.py:164-210 / ibot.py:182-220 / mocov3.py:146-186 / mae.py:195-237)
     def _tap_bn(self):
         if not self.add_norm:
@@ -761,6 +868,7 @@ class ViTBackbone(nn.Module):
     def _extract(self, images: torch.Tensor, n_spatial_from_grid: bool = True, want_cls: bool = False):
         if not images.is_cuda:
             raise lib.MvpError("images must be on the HIP device (no CPU fallback)")
+        self._guard(images)
         eng = self.engine()
         bns, mode = self._tap_bn()
         with torch.no_grad():
@@ -782,6 +890,7 @@ class ViTBackbone(nn.Module):
             raise lib.MvpError("images must be on the HIP device (no CPU fallback)")
         if images.shape[-2] % self.patch_size or images.shape[-1] % self.patch_size:
             raise ValueError("extract_kqv: the image size must be a multiple of the patch size (dino.py:105 has no padding on this path)")
+        self._guard(images)
         with torch.no_grad():
             qkv = self.engine().last_block_qkv(images)
         bs, _, C3 = qkv.shape

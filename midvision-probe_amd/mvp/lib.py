@@ -282,6 +282,10 @@ class TaskMetricsArgs(Struct, c_name="mvp_task_metrics_args"):  # per-image AbsR
                 ("B", _i), ("C", _i), ("Cm", _i), ("HW", _i64), ("form", _i), ("t1", _f), ("t2", _f), ("t3", _f)]
 
 
+class F16ScanArgs(Struct, c_name="mvp_f16_scan_args"):  # range scan of an fp16-form pair operand into a 16-byte record (added within ABI 8)
+    _fields_ = [("hi", _vp), ("record", _vp), ("rows", _i), ("col0", _i), ("cols", _i), ("ld", _i), ("layout", _i)]
+
+
 class BnActArgs(Struct, c_name="mvp_bn_act_args"):  # BatchNorm2d + activation on a few-channel map, forward and backward (added within ABI 8)
     _fields_ = [("x", _vp), ("y", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
                 ("stats", _vp), ("grad_y", _vp), ("grad_x", _vp), ("grad_gamma", _vp), ("grad_beta", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
@@ -455,6 +459,7 @@ SYMBOLS = {
     "mvp_task_prepare": TaskPrepareArgs,
     "mvp_masked_l1_fwd_bwd": MaskedL1Args,
     "mvp_task_metrics": TaskMetricsArgs,
+    "mvp_f16_range_scan": F16ScanArgs,
 }
 
 # the exports that are not `int f(const args*, void* stream)` (None above): name -> (restype, argtypes)

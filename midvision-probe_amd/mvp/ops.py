@@ -724,6 +724,23 @@ def swiglu(h12: torch.Tensor, out, M: int, H: int, *, ld_in: Optional[int] = Non
     _traced("hbm", "swiglu_kernel", 0, float(nb), lambda: lib.call("mvp_swiglu_fwd", a))
 
 
+def f16_range_scan(pair, rows: int, cols: int, record: torch.Tensor, col0: int = 0) -> None:
+    """Scan the fp16 ``hi`` half of columns [col0, col0 + cols) of the first ``rows`` rows of ``pair`` (a Pair — its hi array may be
+    wider than the window and must have unit column stride — or an IlvPair) into ``record``, 4 uint32 words on the device that are
+    accumulated into (max of bits & 0x7FFF, n at +-65504, n non-finite, n scanned): mvp_f16_range_scan.  Nothing else is written."""
+    ilv = isinstance(pair, IlvPair)
+    hi = pair.t if ilv else pair[0]
+    if hi.dim() != 2 or hi.element_size() != 2 or not hi.is_cuda or hi.stride(1) != 1:
+        raise lib.MvpError("f16_range_scan: a 2-D device array of 16-bit words with unit column stride expected")
+    width = hi.shape[1] // 2 if ilv else hi.shape[1]
+    if not (0 < rows <= hi.shape[0] and 0 <= col0 and 0 < cols and col0 + cols <= width):
+        raise lib.MvpError(f"f16_range_scan: rows {rows}, columns [{col0}, {col0 + cols}) outside the operand of {hi.shape[0]} x {width}")
+    if record.dtype not in (torch.uint32, torch.int32) or record.numel() != 4 or not record.is_cuda or not record.is_contiguous():
+        raise lib.MvpError("f16_range_scan: the record is 4 contiguous uint32 words on the device")
+    a = lib.F16ScanArgs(lib.ptr(hi), lib.ptr(record), rows, col0, cols, hi.stride(0), lib.PAIR_A_ILV32 if ilv else lib.PAIR_SEPARATE)
+    _traced("hbm", "f16_range_scan_kernel", 0, float(rows * cols * 2), lambda: lib.call("mvp_f16_range_scan", a))
+
+
 def augment_partials(B: int, device) -> torch.Tensor:
     """The [B, MVP_AUGMENT_PARTIALS] fp64 buffer augment_stats writes and augment_apply reads (no initialisation needed)."""
     return torch.empty(int(lib.load().mvp_augment_partials_bytes(B)) // 8, dtype=torch.float64, device=device).view(B, -1)

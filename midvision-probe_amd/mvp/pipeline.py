@@ -546,12 +546,24 @@ class FeaturePipeline:
     def submit(self, images: torch.Tensor) -> None:
         self.submit_group([images])
 
+    def _range_guard(self, images: torch.Tensor) -> None:
+        """A ViT wrapper's f16x2 range guard (mvp/backbone.py ``resolve_range_guard``), called with every raw batch this pipeline is
+        given and pending only on the first: the wrapper applies its own preprocessing (the resize of BEiT v2 / CroCo / MoCo-v3, MAE's
+        position table) and audits one forward on the caller's stream, before the first eager forward and before any capture (it
+        synchronises once).  A fallback then simply means that the pipeline is built on the 'bf16x3' engine.  Every later call still
+        reads MVP_F16_GUARD and the world size, and, while the guard is armed, builds the engine signature over all parameters (what
+        ``engine()`` does on every forward anyway) to find it resolved."""
+        guard = getattr(self.model, "resolve_range_guard", None)
+        if guard is not None:
+            guard(images)
+
     def submit_group(self, batches) -> None:
         """Enqueue ONE forward over ``batches`` (a list of equal-shaped image batches; a single one = the plain forward)."""
         batches = list(batches)
         G = len(batches)
         if G < 1:
             raise ValueError("empty group")
+        self._range_guard(batches[0])
         self.resolve_group(batches[0])
         if G > 1 and (any(b.shape != batches[0].shape or b.dtype != batches[0].dtype for b in batches) or self.depth == 1):
             raise ValueError("a grouped forward needs equal-shaped batches and a pipeline of depth >= 2")
@@ -562,6 +574,8 @@ class FeaturePipeline:
         the stream, whose first ``batch - carry`` images (when carry > 0) complete the batch the previous span cut; the span may end
         inside a batch again.  ``next()`` hands over the (carry + images) // batch batches the forward completes, in order."""
         pieces = list(pieces)
+        if pieces:
+            self._range_guard(pieces[0])
         if not pieces or self.depth != 2 or self.chains != 1:
             raise ValueError("a span forward needs images and the two-slot, one-stream pipeline of grouped forwards")
         if any(p.shape[1:] != pieces[0].shape[1:] or p.dtype != pieces[0].dtype for p in pieces):

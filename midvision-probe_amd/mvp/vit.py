@@ -40,7 +40,9 @@ def parse_precision(p) -> int:
     """'bf16x3' (three bf16 products per contraction, ~1e-5 on the features), 'f16x2' (the four GEMMs of every block
     with two fp16 products over compensated fp16 pairs, include/mvp_hip.h MVP_PREC_F16X2; everything else as in bf16x3; the same
     ~1e-5 on the features, |activation| <= 65504), 'bf16' (one product: fails the 1e-3 feature contract).  The ViT wrappers run
-    'f16x2' unless told otherwise (backbone.default_precision()); a bare ViTEngine(...) without ``precision`` is a 'bf16x3' engine."""
+    'f16x2' unless told otherwise (backbone.default_precision()); a bare ViTEngine(...) without ``precision`` is a 'bf16x3' engine.
+    'f16x2' saturates silently beyond fp16's range: the wrappers' range guard (``range_guard=`` / MVP_F16_GUARD, backbone.ViTBackbone)
+    audits one forward with ``RangeAudit`` and warns, raises or falls back to 'bf16x3'."""
     if p in (PREC_BF16, PREC_BF16X3, lib.PREC_F16X2):
         return p
     s = str(p).lower()
@@ -222,6 +224,42 @@ def sam_window_index(B: int, gh: int, gw: int, w: int) -> Tuple[torch.Tensor, to
     live = part >= 0
     unpart[part[live]] = torch.arange(part.numel())[live]
     return part.to(torch.int32).contiguous(), unpart.to(torch.int32).contiguous()
+
+
+class RangeAudit:
+    """The record of one or more audited forwards of ``engine`` (``forward_taps(..., audit=...)``, ``last_block_qkv(..., audit=...)``):
+    one zeroed [S, 4] uint32 device tensor, a row per site — an fp16-form operand of a block, scanned in the buffer its consumer reads,
+    right before that consumer (mvp_f16_range_scan) — and the sites' names, which are the strings ``ViTEngine._check_f16_range`` uses.
+    The scans run on the forward's stream without a sync and touch nothing but the record; ``read()`` is the one device-to-host copy.
+    An engine without fp16-form operands ('bf16x3' without ``att_qk_f16``) has no sites: auditing it is a no-op."""
+
+    def __init__(self, engine: "ViTEngine"):
+        self.sites: List[str] = engine.audit_sites()
+        self.blocks: List[int] = [int(s.split(":")[0].split()[1]) for s in self.sites]
+        self._row = {s: j for j, s in enumerate(self.sites)}
+        # (allocated as int32 and viewed: zero fill and copies of the unsigned types are not available in every torch build)
+        self.record = torch.zeros(max(len(self.sites), 1), 4, dtype=torch.int32, device=engine.device).view(torch.uint32)[:len(self.sites)]
+
+    def scan(self, site: str, pair, rows: int, cols: int, col0: int = 0) -> None:
+        ops.f16_range_scan(pair, rows, cols, self.record[self._row[site]], col0)
+
+    def read(self) -> List[dict]:
+        """One dict(site, block, max_abs, n_sat, n_nonfinite, n_scanned) per site, in forward order (one copy, which waits for the
+        stream's work as any device-to-host copy does).  ``max_abs`` is the fp16 value of the largest magnitude seen (inf / nan included)."""
+        if not self.sites:
+            return []
+        words = (self.record.view(torch.int32).cpu().to(torch.int64) & 0xFFFFFFFF).tolist()
+        out = []
+        for site, blk, (mx, n_sat, n_nonf, n) in zip(self.sites, self.blocks, words):
+            max_abs = float(torch.tensor([mx], dtype=torch.int32).to(torch.int16).view(torch.float16)[0])
+            out.append(dict(site=site, block=blk, max_abs=max_abs, n_sat=int(n_sat), n_nonfinite=int(n_nonf), n_scanned=int(n)))
+        return out
+
+
+def tripped_sites(report: Sequence[dict]) -> List[dict]:
+    """The rows of a ``RangeAudit.read()`` report with a saturated or non-finite element (an exactly representable 65504 counts, as in
+    ``ViTEngine._check_f16_range``)."""
+    return [r for r in report if r["n_sat"] + r["n_nonfinite"] > 0]
 
 
 class ViTEngine:
@@ -573,11 +611,26 @@ class ViTEngine:
             if not bool((t.view(torch.float16).abs() < 65504.0).all()):  # (NaN fails the comparison too)
                 raise lib.MvpError(f"f16x2: {what} holds values beyond fp16's range (|v| >= 65504): run this model with precision='bf16x3' (MVP_PRECISION=bf16x3)")
 
-    def _ln1_qkv(self, i: int, ws: dict, M: int, out_f32: Optional[torch.Tensor] = None) -> None:
+    def _act_site(self) -> str:
+        return {"gelu": "GELU(fc1) output", "swiglu": "SwiGLU gate output silu(x1) * x2"}.get(self.act_name, f"{self.act_name}(fc1) output")
+
+    def audit_sites(self) -> List[str]:
+        """The names of the fp16-form operands a forward of this engine reads, in forward order (``RangeAudit``): per block the four
+        activation operands of an f16x2 engine's GEMMs and, with ``att_qk_f16``, the Q / K the attention kernel reads."""
+        out = []
+        for i in range(self.depth):
+            kinds = (["LayerNorm 1 output"] if self.f16x2 else []) + (["Q / K"] if self.att_qk_f16 else [])
+            kinds += ["attention output", "LayerNorm 2 output", self._act_site()] if self.f16x2 else []
+            out += [f"block {i}: {k}" for k in kinds]
+        return out
+
+    def _ln1_qkv(self, i: int, ws: dict, M: int, out_f32: Optional[torch.Tensor] = None, audit: Optional[RangeAudit] = None) -> None:
         """LayerNorm 1 and the fused qkv projection of block i, into ws['qkv'] in the forms the attention kernel reads — or, with
         ``out_f32`` (last_block_qkv: no attention follows), as plain fp32 [M, 3C] without any f16 output form."""
         blk, C, f2 = self.blocks[i], self.C, self.f16x2
         ops.layernorm(ws["x"], blk["n1w"], blk["n1b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
+        if audit is not None and f2:
+            audit.scan(f"block {i}: LayerNorm 1 output", ws["xn"], M, C)
         # bf16x3: the V third of qkv leaves the GEMM as hi = fp16, lo = bf16, and the attention kernel holds its probabilities as one
         # fp16 value (csrc/attention.hip, VF16; MVP_ATT_V=pair brings back the bf16-pair probabilities of rounds 1-3)
         # (f16x2: Q and K leave as compensated fp16 pairs too — activation / weight-side form, Q.K^T in two f16 products — unless MVP_ATT_QK=pair;
@@ -587,7 +640,7 @@ class ViTEngine:
                  precision=lib.PREC_F16X2 if f2 else self.precision, w_ilv=blk.get("qkv_w_ilv"),
                  f16_col0=(-2 * C if self.att_qk_f16 else 2 * C) if (pairs and self.att_v_f16) else 0)
 
-    def _sam_attention(self, i: int, ws: dict, B: int, N: int) -> None:
+    def _sam_attention(self, i: int, ws: dict, B: int, N: int, audit: Optional[RangeAudit] = None) -> None:
         """LayerNorm 1 up to the attention output ws['ao'] of a SAM block.  Windowed block: LN1, gather into windows (pad rows zero AFTER the
         norm, so they pass the qkv GEMM and are real keys with k = b_k, v = b_v, as in segment_anything), qkv GEMM over the B * nW * w^2
         padded rows as fp32, relative-position terms + conversion (mvp_relpos_terms), attention per window with the decomposed bias, gather
@@ -604,44 +657,57 @@ class ViTEngine:
         else:
             Bp, Np, kh, kw, a_in, ao = B, N, gh, gw, ws["xn"], ws["ao"]
         Mp = Bp * Np
+        if audit is not None and f2:  # (a windowed block: the gathered rows the GEMM reads, zero pad rows included)
+            audit.scan(f"block {i}: LayerNorm 1 output", a_in, Mp, C)
         ops.gemm(a_in, blk["qkv_w"], Mp, 3 * C, C, bias=blk["qkv_b"], out_f32=ws["qkv_f32"], precision=lib.PREC_F16X2 if f2 else pr, w_ilv=blk.get("qkv_w_ilv"))
         rh, rw = self.sam_rel_tables(i, kh, kw)
         ld = -(-(kh + kw) // 4) * 4
         rel = ws["rel"][:Bp * self.heads * Np * ld].view(Bp * self.heads, Np, ld)
         ops.relpos_terms(ws["qkv_f32"], ws["qkv"], rel, rh, rw, Mp, Np, self.heads, pr, v_f16=self.att_v_f16, qk_f16=self.att_qk_f16)
+        if audit is not None and self.att_qk_f16:
+            audit.scan(f"block {i}: Q / K", ws["qkv"], Mp, 2 * C)
         ops.attention(ws["qkv"], ao, Bp, Np, self.heads, 64 ** -0.5, pr, v_f16=self.att_v_f16, qk_f16=self.att_qk_f16, out_f16=f2, rel=rel, rel_grid=(kh, kw))
         if w:
             ops.gather_rows(ws["aow"], ws["ao"], unpart, Mp, C)
 
-    def run_block(self, i: int, ws: dict, B: int, N: int) -> None:
+    def run_block(self, i: int, ws: dict, B: int, N: int, audit: Optional[RangeAudit] = None) -> None:
+        """Block i over the M = B * N rows of ws['x'].  ``audit``: scan every fp16-form operand in the buffer its consumer reads, right
+        before that consumer (one extra read-only launch per site on this stream; nothing the block computes changes)."""
         blk, C, M, pr = self.blocks[i], self.C, B * N, self.precision
         f2 = self.f16x2
         chk = f2 and self.check_f16_range
+        aud = audit if f2 else None  # the four activation operands exist in fp16 form only in an f16x2 engine
         gp = lib.PREC_F16X2 if f2 else pr  # precision of the four block GEMMs
         x = ws["x"]
         vf16, qk16 = self.att_v_f16, self.att_qk_f16
         if self.sam:
-            self._sam_attention(i, ws, B, N)
+            self._sam_attention(i, ws, B, N, audit)
         elif self.rope_freq is None:
-            self._ln1_qkv(i, ws, M)
+            self._ln1_qkv(i, ws, M, audit=audit)
         else:  # the projection as fp32, then rotation + conversion into the forms the attention kernel reads (mvp_rope2d_qkv)
             gh, gw = ws["grid"]
             cos, sin = self.rope_for(gh, gw)
-            self._ln1_qkv(i, ws, M, out_f32=ws["qkv_f32"])
+            self._ln1_qkv(i, ws, M, out_f32=ws["qkv_f32"], audit=audit)
             ops.rope2d_qkv(ws["qkv_f32"], ws["qkv"], cos, sin, M, N, self.heads, self.n_prefix, gh, gw, pr, v_f16=vf16, qk_f16=qk16)
         if chk:  # (after the projection: ws["xn"] still holds LayerNorm 1's output)
             self._check_f16_range(f"block {i}: LayerNorm 1 output", ws["xn"], M)
         if chk and qk16:
             self._check_f16_range(f"block {i}: Q / K", (ws["qkv"][0][:, :2 * C], ws["qkv"][1][:, :2 * C]), M)
         if not self.sam:
+            if audit is not None and qk16:
+                audit.scan(f"block {i}: Q / K", ws["qkv"], M, 2 * C)
             ops.attention(ws["qkv"], ws["ao"], B, N, self.heads, 64 ** -0.5, pr, v_f16=vf16, qk_f16=qk16, out_f16=f2, bias=blk.get("att_bias"))
         if chk:
             self._check_f16_range(f"block {i}: attention output", ws["ao"], M)
+        if aud is not None:
+            aud.scan(f"block {i}: attention output", ws["ao"], M, C)
         ops.gemm(ws["ao"], blk["proj_w"], M, C, C, bias=blk["proj_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("proj_w_ilv"),
                  col_scale=blk["ls1"])
         ops.layernorm(x, blk["n2w"], blk["n2b"], ws["xn"], M, C, self.ln_eps, out_f16=f2)
         if chk:
             self._check_f16_range(f"block {i}: LayerNorm 2 output", ws["xn"], M)
+        if aud is not None:
+            aud.scan(f"block {i}: LayerNorm 2 output", ws["xn"], M, C)
         if self.swiglu:  # w12 as fp32 [M, 2H], then silu(gate) * value into the A operand of w3 (columns H .. hidden-1 zero)
             ops.gemm(ws["xn"], blk["fc1_w"], M, self.fc1_out, C, bias=blk["fc1_b"], out_f32=ws["h12"], precision=gp, w_ilv=blk.get("fc1_w_ilv"))
             ops.swiglu(ws["h12"], ws["hmid"], M, self.swiglu_h, ld_out=self.hidden, precision=gp)
@@ -651,12 +717,14 @@ class ViTEngine:
         if chk:
             what = {"gelu": "GELU(fc1) output", "swiglu": "SwiGLU gate output silu(x1) * x2"}.get(self.act_name, f"{self.act_name}(fc1) output")
             self._check_f16_range(f"block {i}: {what}", ws["hmid"], M)
+        if aud is not None:
+            aud.scan(f"block {i}: {self._act_site()}", ws["hmid"], M, self.hidden)
         ops.gemm(ws["hmid"], blk["fc2_w"], M, C, self.hidden, bias=blk["fc2_b"], residual=x, out_f32=x, precision=gp, w_ilv=blk.get("fc2_w_ilv"),
                  col_scale=blk["ls2"])
 
     def forward_taps(self, images: torch.Tensor, layers: Sequence[int], *, bn: Optional[Sequence[dict]] = None,
                      bn_mode: int = 0, pack: bool = True, tap_input_of_block: bool = False, want_cls: bool = False, groups: int = 1,
-                     replay_after_norm: bool = False):
+                     replay_after_norm: bool = False, audit: Optional[RangeAudit] = None):
         """Run blocks up to the last tapped one; at each tap apply the (train-mode) tap BN and
         emit the NCHW map (+ token-major packing).  ``bn[j]`` = dict(weight,bias,running_mean,
         running_var) tensors or None; bn_mode: 0 train stats, 1 eval, 2 no norm.
@@ -675,7 +743,10 @@ class ViTEngine:
         (carry + images) // batch batches this forward completes.
         ``replay_after_norm`` (BEiT v2's wrapper, beit_v2.py:261-265): before the tapped loop, run ALL ``depth`` blocks over the token
         stream and apply ``fc_norm`` to every row of it in place; the tapped loop then runs the blocks AGAIN on that result.  Blocks and
-        LayerNorm are per row, so grouped and span forwards and graph capture need nothing new."""
+        LayerNorm are per row, so grouped and span forwards and graph capture need nothing new.
+        ``audit`` (a ``RangeAudit`` of this engine): every block run by this forward — the replay pass included, into the same sites —
+        also scans its fp16-form operands into the audit's record, on this stream and without a sync; the taps are bit for bit those of
+        an unaudited forward.  ``audit.read()`` afterwards."""
         if want_cls and not self.has_cls:
             raise lib.MvpError("want_cls: this model has no CLS token (n_prefix = 0); use output 'dense' or 'gap'")
         span = groups if isinstance(groups, pipeline.Span) else None
@@ -693,7 +764,7 @@ class ViTEngine:
             if self.fc_norm is None:
                 raise lib.MvpError("replay_after_norm: the state dict has no fc_norm.weight / fc_norm.bias")
             for i in range(self.depth):
-                self.run_block(i, ws, Bt, N)
+                self.run_block(i, ws, Bt, N, audit)
             ops.layernorm(ws["x"], self.fc_norm[0], self.fc_norm[1], None, Bt * N, self.C, self.ln_eps, out_f32=ws["x"])
         x_bn, store, bn_ws, packs, out = self._tap_buffers(ws, span, G, B, carry, gh, gw, layers, pack, want_cls)
         t = SimpleNamespace(ws=ws, x_bn=x_bn, store=store, bn_ws=bn_ws, packs=packs, out=out, Bt=Bt, N=N, hw=gh * gw, G=G, B=B, carry=carry, tail=tail,
@@ -706,7 +777,7 @@ class ViTEngine:
                 self._tap(t, layers.index(i))
                 if len(t.outs[0]) == len(layers):
                     break
-            self.run_block(i, ws, Bt, N)
+            self.run_block(i, ws, Bt, N, audit)
             if (not tap_input_of_block) and i in layers:
                 self._tap(t, layers.index(i))
                 if len(t.outs[0]) == len(layers):
@@ -779,16 +850,17 @@ class ViTEngine:
                 t.running[g].append((stats[g, j], b["running_mean"], b["running_var"], b.get("num_batches_tracked"), C))
             t.outs[g].append(nchw[g])
 
-    def last_block_qkv(self, images: torch.Tensor) -> torch.Tensor:
+    def last_block_qkv(self, images: torch.Tensor, audit: Optional[RangeAudit] = None) -> torch.Tensor:
         """The fused qkv projection of the LAST block (fp32 [B, N, 3C]: q | k | v, heads side by side) — what the reference captures
         with a forward hook on ``blocks[-1].attn.qkv`` (dino.py:82-113).  Blocks 0 .. depth-2 run as usual; the last block stops after
-        LayerNorm 1 and the projection (its attention output is never used on that path)."""
+        LayerNorm 1 and the projection (its attention output is never used on that path).  ``audit``: as in ``forward_taps``; of the
+        last block only LayerNorm 1's output is an operand here."""
         ws, B, gh, gw = self.tokens(images)
         N = self.n_prefix + gh * gw
         for i in range(self.depth - 1):
-            self.run_block(i, ws, B, N)
+            self.run_block(i, ws, B, N, audit)
         out = torch.empty(B * N, 3 * self.C, dtype=torch.float32, device=self.device)
-        self._ln1_qkv(self.depth - 1, ws, B * N, out_f32=out)
+        self._ln1_qkv(self.depth - 1, ws, B * N, out_f32=out, audit=audit)
         return out.view(B, N, 3 * self.C)
 
     def forward_tokens(self, images: torch.Tensor, n_blocks: Optional[int] = None) -> torch.Tensor:
