@@ -8,7 +8,7 @@
 // value over the whole source image at the moment contrast is reached in that image's order:
 // Launch 1, grid = (MVP_AUGMENT_PARTIALS, B): workgroup k of image b walks the pixel groups g (4 pixels) with (g / 256) % 32 == k, runs
 // the operations that precede contrast, and sums the grey values in fp64: per lane in pixel order, a butterfly inside the wave, the four
-// waves in a fixed order through LDS.  One partial per workgroup (0 for an image whose jitter is off): no atomics.
+// waves in a fixed order through LDS (csrc/mvp_reduce.h).  One partial per workgroup (0 for an image whose jitter is off): no atomics.
 // Launch 2, grid = (rows of 256 lanes, B): a lane owns four consecutive output x of one row.  It adds the image's partials in index
 // order (every lane the same 32 additions: every workgroup gets the same bits), builds the composed map, gathers the source pixel of the
 // image, the depth and the normals, runs the jitter chain in registers, normalises and writes each plane with one 16-byte store (scalar
@@ -17,7 +17,7 @@
 // form are byte loads of 3-byte pixels, those of the fp32 form dword loads per plane.
 #include <math.h>
 
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
@@ -132,11 +132,11 @@ __device__ __forceinline__ void au_load_group(const au_params& p, int b, int HW,
 
 template <bool U8>
 __global__ __launch_bounds__(AU_THREADS) void augment_stats_kernel(const au_params p) {
-  __shared__ double red[AU_THREADS / 64];
+  __shared__ double red[AU_THREADS / 64][1];
   const int b = blockIdx.y, k = blockIdx.x;
   const int32_t* t = p.table + (size_t)b * AU_K;
   const int HW = p.H * p.W, ngroups = (HW + 3) >> 2;
-  double acc = 0.0;
+  double acc[1] = {0.0};
   if (t[0] & 1) {  // uniform
     const au_jit jit = au_read_jit(t);
     // one group per trip: the walk is bound by the jitter arithmetic, not by load latency (four groups in flight per lane measured
@@ -148,15 +148,12 @@ __global__ __launch_bounds__(AU_THREADS) void augment_stats_kernel(const au_para
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         au_chain<true>(r[j], gg[j], bb[j], jit, 0.f);
-        acc += j < n ? (double)au_grey(r[j], gg[j], bb[j]) : 0.0;
+        acc[0] += j < n ? (double)au_grey(r[j], gg[j], bb[j]) : 0.0;
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) p.partials[(size_t)b * AU_P + k] = (red[0] + red[1]) + (red[2] + red[3]);
+  block_sum_once<1>(acc, red);
+  if (threadIdx.x == 0) p.partials[(size_t)b * AU_P + k] = acc[0];
 }
 
 // index i reflected into [0, n) without repeating the edge (reflect-101), any i
@@ -247,13 +244,11 @@ __global__ __launch_bounds__(AU_THREADS) void augment_apply_kernel(const au_para
   }
 }
 
-inline bool au_aligned(const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; }
-
 inline bool au_source_ok(const void* image, const int32_t* table, int B, int H, int W, int image_u8) {
   if (!image || !table || B <= 0 || B > 65535 || H < 4 || W < 4 || H > AU_MAX_SIDE || W > AU_MAX_SIDE) return false;
   if ((int64_t)H * W > ((int64_t)1 << 29)) return false;
   if (image_u8 != 0 && image_u8 != 1) return false;
-  return au_aligned(table, 4) && (image_u8 || au_aligned(image, 4));
+  return aligned_to(table, 4) && (image_u8 || aligned_to(image, 4));
 }
 
 }  // namespace
@@ -262,11 +257,11 @@ extern "C" int64_t mvp_augment_partials_bytes(int B) { return B > 0 ? (int64_t)B
 
 extern "C" int mvp_augment_stats(const mvp_augment_stats_args* a, void* stream) {
   if (!a || !au_source_ok(a->image, a->params, a->B, a->H, a->W, a->image_u8)) return MVP_EINVAL;
-  if (!a->partials || !au_aligned(a->partials, 8) || a->partials_bytes < mvp_augment_partials_bytes(a->B)) return MVP_EINVAL;
+  if (!a->partials || !aligned_to(a->partials, 8) || a->partials_bytes < mvp_augment_partials_bytes(a->B)) return MVP_EINVAL;
   au_params p = {};
   p.image = a->image; p.table = a->params; p.partials = a->partials;
   p.B = a->B; p.H = a->H; p.W = a->W;
-  p.vec = ((a->H * a->W) & 3) == 0 && au_aligned(a->image, a->image_u8 ? 4 : 16);
+  p.vec = ((a->H * a->W) & 3) == 0 && aligned_to(a->image, a->image_u8 ? 4 : 16);
   const dim3 grid(AU_P, (unsigned)a->B);
   hipStream_t s = (hipStream_t)stream;
   if (a->image_u8) hipLaunchKernelGGL(augment_stats_kernel<true>, grid, dim3(AU_THREADS), 0, s, p);
@@ -279,9 +274,9 @@ extern "C" int mvp_augment_apply(const mvp_augment_apply_args* a, void* stream) 
   if (!a || !au_source_ok(a->image, a->params, a->B, a->H, a->W, a->image_u8)) return MVP_EINVAL;
   if (!a->depth || !a->out_image || !a->out_depth || (a->snorm == nullptr) != (a->out_snorm == nullptr)) return MVP_EINVAL;
   if (a->Ho <= 0 || a->Wo <= 0 || a->Ho > AU_MAX_SIDE || a->Wo > AU_MAX_SIDE) return MVP_EINVAL;
-  if (a->partials && (!au_aligned(a->partials, 8) || a->partials_bytes < mvp_augment_partials_bytes(a->B))) return MVP_EINVAL;
-  if (!au_aligned(a->depth, 4) || !au_aligned(a->snorm, 4) || !au_aligned(a->out_image, 4) || !au_aligned(a->out_depth, 4) ||
-      !au_aligned(a->out_snorm, 4))
+  if (a->partials && (!aligned_to(a->partials, 8) || a->partials_bytes < mvp_augment_partials_bytes(a->B))) return MVP_EINVAL;
+  if (!aligned_to(a->depth, 4) || !aligned_to(a->snorm, 4) || !aligned_to(a->out_image, 4) || !aligned_to(a->out_depth, 4) ||
+      !aligned_to(a->out_snorm, 4))
     return MVP_EINVAL;
   if (!(a->std_r != 0.f) || !(a->std_g != 0.f) || !(a->std_b != 0.f)) return MVP_EINVAL;
   au_params p = {};
@@ -290,7 +285,7 @@ extern "C" int mvp_augment_apply(const mvp_augment_apply_args* a, void* stream) 
   p.B = a->B; p.H = a->H; p.W = a->W; p.Ho = a->Ho; p.Wo = a->Wo;
   p.mean[0] = a->mean_r; p.mean[1] = a->mean_g; p.mean[2] = a->mean_b;
   p.std[0] = a->std_r; p.std[1] = a->std_g; p.std[2] = a->std_b;
-  p.vec = (a->Wo & 3) == 0 && au_aligned(a->out_image, 16) && au_aligned(a->out_depth, 16) && au_aligned(a->out_snorm, 16);
+  p.vec = (a->Wo & 3) == 0 && aligned_to(a->out_image, 16) && aligned_to(a->out_depth, 16) && aligned_to(a->out_snorm, 16);
   const int64_t lanes = (int64_t)((a->Wo + 3) >> 2) * a->Ho;
   const dim3 grid((unsigned)((lanes + AU_THREADS - 1) / AU_THREADS), (unsigned)a->B);
   hipStream_t s = (hipStream_t)stream;

@@ -3,8 +3,8 @@
 //   mvp_dwconv7_ln_fwd   depthwise 7x7 (stride 1, zero padding 3) + LayerNorm over the channels -> the A operand of fc1
 //   mvp_grn_stats        V2's global response normalisation, statistics: G[b, c] = ||h[b, :, c]||_2, N = G / (mean_c G + 1e-6)
 //   mvp_grn_apply        gamma (h N) + beta + h -> the A operand of fc2
-// fp32 arithmetic in a fixed order everywhere (no atomics): the same inputs give the same bits.
-#include "mvp_common.h"
+// fp32 arithmetic in a fixed order everywhere (no atomics): the same inputs give the same bits.  The fp64 mean of GRN: csrc/mvp_reduce.h.
+#include "mvp_reduce.h"
 
 namespace {
 
@@ -192,21 +192,18 @@ __global__ __launch_bounds__(64) void grn_partial_kernel(const mvp_grn_args p, c
 
 // One workgroup per image: G = sqrt(sum of the partials, slabs in order), mean over the channels (fp64, fixed order), N.
 __global__ __launch_bounds__(256) void grn_finish_kernel(const mvp_grn_args p, const int S, const double* __restrict__ partial) {
-  __shared__ double red[4];
+  __shared__ double red[4][1];
   const int b = blockIdx.x, t = threadIdx.x;
-  double local = 0.0;
+  double local[1] = {0.0};
   for (int c = t; c < p.C4; c += 256) {
     double a = 0.0;
     for (int s = 0; s < S; ++s) a += partial[((size_t)b * S + s) * p.C4 + c];
     const float g = (float)sqrt(a);
     p.G[(size_t)b * p.C4 + c] = g;
-    local += (double)g;
+    local[0] += (double)g;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o, 64);
-  if ((t & 63) == 0) red[t >> 6] = local;
-  __syncthreads();
-  const double mean = ((red[0] + red[1]) + (red[2] + red[3])) / (double)p.C4;
+  block_sum<1>(local, red);
+  const double mean = local[0] / (double)p.C4;
   const float den = (float)mean + 1e-6f;
   for (int c = t; c < p.C4; c += 256) p.N[(size_t)b * p.C4 + c] = p.G[(size_t)b * p.C4 + c] / den;  // (this thread wrote G[b, c] itself)
 }
@@ -284,7 +281,7 @@ extern "C" int64_t mvp_grn_workspace_bytes(int B, int HW, int C4) {
 
 extern "C" int mvp_grn_stats(const mvp_grn_args* a, void* stream) {
   if (!grn_shape_ok(a) || !a->h || !a->G || !a->N || !a->workspace) return MVP_EINVAL;
-  if (((uintptr_t)a->workspace & 7) || a->workspace_bytes < mvp_grn_workspace_bytes(a->B, a->HW, a->C4)) return MVP_EINVAL;
+  if (!aligned_to(a->workspace, 8) || a->workspace_bytes < mvp_grn_workspace_bytes(a->B, a->HW, a->C4)) return MVP_EINVAL;
   const int S = grn_slabs(a->HW);
   double* partial = (double*)a->workspace;
   hipLaunchKernelGGL(grn_partial_kernel, dim3((a->C4 / 4 + 63) / 64, S, a->B), dim3(64), 0, (hipStream_t)stream, *a, S, partial);

@@ -17,7 +17,7 @@
 // launch at every size measured, and this one 9 us at the small ones (profiles/f16_scan_bench.txt).  Supposed cause, not isolated by
 // a measurement of its own (the two shapes differ in workgroup size AND atomic count): the atomics all land on one 16-byte line and
 // are served one after the other, which would be about 12 ns each.
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
@@ -58,11 +58,6 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
   return v;
 }
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
 
 // Chunk g of the window = 8 columns from col0 + 8 (g % nv) of row g / nv; (row, c) are carried along instead of divided out per step.
 template <bool ILV>
@@ -98,9 +93,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void f16_range_scan_kernel(const mvp_
       if (live[u]) scan_chunk(v[u], a);
   }
   a.max_bits = wave_max_u32(a.max_bits);
-  a.n_sat = wave_sum_u32(a.n_sat);
-  a.n_nonfinite = wave_sum_u32(a.n_nonfinite);
-  a.n_scanned = wave_sum_u32(a.n_scanned);
+  a.n_sat = wave_sum(a.n_sat);
+  a.n_nonfinite = wave_sum(a.n_nonfinite);
+  a.n_scanned = wave_sum(a.n_scanned);
   __shared__ unsigned part[SCAN_THREADS / 64][4];
   const unsigned wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63u) == 0u) {

@@ -1,26 +1,16 @@
 // Training losses with analytic gradients, deterministic reductions (per-block fp64 partials
-// combined in a fixed order; no float atomics):
+// combined in a fixed order; no float atomics: csrc/mvp_reduce.h has the rule and the sums):
 //   DepthLoss   = 10*sig_loss + 0.5*gradient_loss   (evals/utils/losses.py:54-74,97-154)
 //   angular_loss (optionally uncertainty-aware)      (evals/utils/losses.py:157-182)
 // Reference quirks are reproduced on purpose: target > max_depth is zeroed in place (Q2); the
 // "gradient" term pairs batch entries j and j+2 of the stride-{1,2,4,6} sub-batches (Q1).
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
 constexpr int DL_NCH = 32;   // chunks per image in the statistics pass
 constexpr int DL_NCH2 = 512; // chunks in the pair pass
 constexpr int DL_SCAL = 16;  // fp64 scalars
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  // deterministic: wave shuffle tree then fixed-order sum over the 4 waves
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 struct DLWs {
   float* ld;       // [B*HW]
@@ -41,12 +31,12 @@ __device__ __host__ inline DLWs dl_ws(void* ws, int B, int64_t HW) {
 }
 
 __global__ __launch_bounds__(256) void dl_stats_kernel(const mvp_depth_loss_args p) {
-  __shared__ double red[4];
+  __shared__ double red[4][3];
   const DLWs w = dl_ws(p.workspace, p.B, p.HW);
   const int b = blockIdx.y, ch = blockIdx.x;
   const int64_t per = (p.HW + DL_NCH - 1) / DL_NCH;
   const int64_t i0 = ch * per, i1 = min(p.HW, i0 + per);
-  double s1 = 0.0, s2 = 0.0, cnt = 0.0;
+  double v[3] = {0.0, 0.0, 0.0};  // sum g, sum g^2, valid pixels
   for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
     const int64_t o = (int64_t)b * p.HW + i;
     float t = p.target[o];
@@ -57,25 +47,23 @@ __global__ __launch_bounds__(256) void dl_stats_kernel(const mvp_depth_loss_args
     float g = 0.f;
     if (t > 0.f) {
       g = logf(p.pred[o] + p.eps) - logf(t + p.eps);
-      cnt += 1.0;
+      v[2] += 1.0;
     }
     w.ld[o] = g;
-    s1 += (double)g;
-    s2 += (double)g * (double)g;
+    v[0] += (double)g;
+    v[1] += (double)g * (double)g;
   }
-  s1 = block_sum(s1, red);
-  s2 = block_sum(s2, red);
-  cnt = block_sum(cnt, red);
+  block_sum<3>(v, red);
   if (threadIdx.x == 0) {
     double* o = w.partA + ((int64_t)b * DL_NCH + ch) * 3;
-    o[0] = s1; o[1] = s2; o[2] = cnt;
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
   }
 }
 
 __device__ __forceinline__ int dl_stride(int k) { return k == 0 ? 1 : (k == 1 ? 2 : (k == 2 ? 4 : 6)); }
 
 __global__ __launch_bounds__(256) void dl_pairs_kernel(const mvp_depth_loss_args p) {
-  __shared__ double red[4];
+  __shared__ double red[4][4];
   const DLWs w = dl_ws(p.workspace, p.B, p.HW);
   const int64_t per = (p.HW + DL_NCH2 - 1) / DL_NCH2;
   const int64_t i0 = blockIdx.x * per, i1 = min(p.HW, i0 + per);
@@ -114,35 +102,25 @@ __global__ __launch_bounds__(256) void dl_pairs_kernel(const mvp_depth_loss_args
       acc[k] += (double)a;
     }
   }
+  block_sum<4>(acc, red);
+  if (threadIdx.x == 0) {
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double v = block_sum(acc[k], red);
-    if (threadIdx.x == 0) w.partB[blockIdx.x * 4 + k] = v;
+    for (int k = 0; k < 4; ++k) w.partB[blockIdx.x * 4 + k] = acc[k];
   }
 }
 
 __global__ __launch_bounds__(256) void dl_finalize_kernel(const mvp_depth_loss_args p) {
-  __shared__ double red[4];
+  __shared__ double red2[4][2], red4[4][4];
   __shared__ double cntb[1024];
   const DLWs w = dl_ws(p.workspace, p.B, p.HW);
-  double s1 = 0.0, s2 = 0.0;
-  for (int i = threadIdx.x; i < p.B * DL_NCH; i += 256) {
-    s1 += w.partA[i * 3];
-    s2 += w.partA[i * 3 + 1];
-  }
-  s1 = block_sum(s1, red);
-  s2 = block_sum(s2, red);
+  double s12[2], pr[4];
+  fold_rows<2>(w.partA, p.B * DL_NCH, 3, s12, red2);  // columns 0 and 1 of [B * DL_NCH][3]
+  fold_rows<4>(w.partB, DL_NCH2, 4, pr, red4);
+  const double s1 = s12[0], s2 = s12[1];
   for (int b = threadIdx.x; b < p.B; b += 256) {
     double c = 0.0;
     for (int ch = 0; ch < DL_NCH; ++ch) c += w.partA[((int64_t)b * DL_NCH + ch) * 3 + 2];
     cntb[b] = c;
-  }
-  double pr[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    double a = 0.0;
-    for (int i = threadIdx.x; i < DL_NCH2; i += 256) a += w.partB[i * 4 + k];
-    pr[k] = block_sum(a, red);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -238,13 +216,13 @@ __device__ __forceinline__ void dlf_pixel(const mvp_depth_loss_args& p, int64_t 
 }
 
 __global__ __launch_bounds__(256) void dlf_stats_kernel(const mvp_depth_loss_args p) {
-  __shared__ double red[4];
+  __shared__ double red[4][6];
   __shared__ int scnt[16];
   const DLFWs w = dlf_ws(p.workspace, p.B, p.HW);
   const int64_t per = (p.HW + gridDim.x - 1) / gridDim.x;
   const int64_t i0 = blockIdx.x * per, i1 = min(p.HW, i0 + per);
   if (threadIdx.x < 16) scnt[threadIdx.x] = 0;
-  double s1 = 0.0, s2 = 0.0, acc[4] = {0.0, 0.0, 0.0, 0.0};
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // s1, s2, pair sums of strides 1, 2, 4, 6
   int cnt[16];
 #pragma unroll
   for (int b = 0; b < 16; ++b) cnt[b] = 0;
@@ -254,8 +232,8 @@ __global__ __launch_bounds__(256) void dlf_stats_kernel(const mvp_depth_loss_arg
     dlf_pixel<true>(p, i, g, ok, pr);
 #pragma unroll
     for (int b = 0; b < 16; ++b) {
-      s1 += (double)g[b];
-      s2 += (double)g[b] * (double)g[b];
+      v[0] += (double)g[b];
+      v[1] += (double)g[b] * (double)g[b];
       cnt[b] += ok[b] ? 1 : 0;
     }
 #pragma unroll
@@ -265,50 +243,39 @@ __global__ __launch_bounds__(256) void dlf_stats_kernel(const mvp_depth_loss_arg
 #pragma unroll
       for (int b1 = 0; b1 + 2 * s < 16; b1 += s)
         if (ok[b1] && ok[b1 + 2 * s]) a += fabsf(g[b1] - g[b1 + 2 * s]);
-      acc[k] += (double)a;
+      v[2 + k] += (double)a;
     }
   }
   __syncthreads();
 #pragma unroll
   for (int b = 0; b < 16; ++b) {
-    int c = cnt[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    const int c = (int)wave_sum((unsigned)cnt[b]);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&scnt[b], c);  // integers: exact in any order
   }
-  s1 = block_sum(s1, red);
-  s2 = block_sum(s2, red);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) acc[k] = block_sum(acc[k], red);
-  __syncthreads();
+  block_sum<6>(v, red);  // its second barrier also orders the atomics above before the read of scnt below
   if (threadIdx.x == 0) {
     double* o = w.part + (int64_t)blockIdx.x * 6;
-    o[0] = s1; o[1] = s2; o[2] = acc[0]; o[3] = acc[1]; o[4] = acc[2]; o[5] = acc[3];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = v[k];
   }
   if (threadIdx.x < 16) w.cnt[blockIdx.x * 16 + threadIdx.x] = scnt[threadIdx.x];
 }
 
 __global__ __launch_bounds__(256) void dlf_grad_kernel(const mvp_depth_loss_args p, const int nb) {
-  __shared__ double red[4];
+  __shared__ double red[4][6];
   __shared__ int scnt[16];
   __shared__ float coef[8];
   const DLFWs w = dlf_ws(p.workspace, p.B, p.HW);
   // every block reduces the nb partial rows itself, in the same fixed order: identical scalars everywhere, no finalize launch
   if (threadIdx.x < 16) scnt[threadIdx.x] = 0;
   __syncthreads();
-  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   int c16 = 0;
-  for (int r = threadIdx.x; r < nb; r += 256) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] += w.part[(int64_t)r * 6 + k];
-  }
   for (int e = threadIdx.x; e < nb * 16; e += 256) {  // e % 16 is the same image for every e of a thread (256 % 16 == 0)
     c16 += w.cnt[e];
   }
   if (c16) atomicAdd(&scnt[threadIdx.x & 15], c16);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) v[k] = block_sum(v[k], red);
-  __syncthreads();
+  double v[6];
+  fold_rows<6>(w.part, nb, 6, v, red);  // its second barrier also orders the atomics above before the read of scnt below
   if (threadIdx.x == 0) {
     double n = 0.0;
     for (int b = 0; b < p.B; ++b) n += (double)scnt[b];
@@ -406,18 +373,17 @@ __device__ __forceinline__ AngPix ang_pixel(const mvp_angular_loss_args& p, int6
 }
 
 __global__ __launch_bounds__(256) void ang_stats_kernel(const mvp_angular_loss_args p, double* part) {
-  __shared__ double red[4];
+  __shared__ double red[4][2];
   const int64_t total = (int64_t)p.B * p.HW;
-  double s = 0.0, c = 0.0;
+  double v[2] = {0.0, 0.0};  // sum of the losses, masked pixels
   for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)AL_NB * 256) {
     if (p.mask[o]) {
-      s += (double)ang_pixel(p, o / p.HW, o % p.HW, false).loss;
-      c += 1.0;
+      v[0] += (double)ang_pixel(p, o / p.HW, o % p.HW, false).loss;
+      v[1] += 1.0;
     }
   }
-  s = block_sum(s, red);
-  c = block_sum(c, red);
-  if (threadIdx.x == 0) { part[blockIdx.x * 2] = s; part[blockIdx.x * 2 + 1] = c; }
+  block_sum<2>(v, red);
+  if (threadIdx.x == 0) { part[blockIdx.x * 2] = v[0]; part[blockIdx.x * 2 + 1] = v[1]; }
 }
 
 __global__ void ang_finalize_kernel(const mvp_angular_loss_args p, double* part) {

@@ -11,10 +11,10 @@
 //   mvp_ncut_partition  mean, bipartition, corner rule, seed, 4-connected component of the seed, the rejection rule of pass >= 2,
 //                       painting update and the hole-filled union, all in LDS, one workgroup per image.
 // Every kernel takes a per-image `active` byte (NULL = all active): the workgroups of an inactive image return at once and leave its
-// outputs untouched.  No floating-point atomics anywhere; two calls give the same bits.
+// outputs untouched.  No floating-point atomics anywhere (csrc/mvp_reduce.h has the rule); two calls give the same bits.
 #include <math.h>
 
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
@@ -27,19 +27,13 @@ namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Sum of K doubles per thread over the workgroup, the same bits in every thread: butterfly inside each wave, then the wave partials
 // in wave order.  red: NC_WAVES * K doubles of LDS; synchronises before and after, so red may be reused at once.
 template <int K>
 __device__ __forceinline__ void block_sum_f64(double (&v)[K], double* red) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
 #pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = wave_sum_f64(v[k]);
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
@@ -121,8 +115,8 @@ __global__ __launch_bounds__(256) void ncut_gram_kernel(const float* __restrict_
       s2 = fma((double)v, (double)v, s2);
     }
   }
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
   if (lane == 0) { red[wave][0] = s1; red[wave][1] = s2; }
   __syncthreads();
   if (threadIdx.x < 2) {
@@ -141,8 +135,8 @@ __global__ __launch_bounds__(64) void ncut_sums_kernel(const double* __restrict_
     s1 += part[((size_t)b * ntiles + t) * 2];
     s2 += part[((size_t)b * ntiles + t) * 2 + 1];
   }
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
   if (lane == 0) { sums[2 * b] = s1; sums[2 * b + 1] = s2; }
 }
 

@@ -1,24 +1,29 @@
-// Validation metrics as fused masked reductions (per-image fp64 partials, fixed-order combine):
+// Validation metrics as fused masked reductions (per-image fp64 partials, fixed-order combine: csrc/mvp_reduce.h):
 //   depth : evaluate_depth global metrics + optional match_scale_and_shift  (evals/utils/metrics.py:106-178,742-780)
 //   snorm : evaluate_surface_norm global metrics                             (evals/utils/metrics.py:397-440)
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
 constexpr int MT_NCH = 32;  // chunks per image
 
-__device__ __forceinline__ double blk_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
+// the depth ratio max(g / q, q / g) that the delta thresholds see, and the error g - q (not its square: dm_partial squares it in
+// fp64, mb_partial in fp32, and the bins of the two must not change)
+__device__ __forceinline__ float depth_ratio(float g, float q, float& err) {
+  err = g - q;
+  return fmaxf(g / fmaxf(q, 1e-9f), q / fmaxf(g, 1e-9f));
+}
+
+// the angle in degrees between a predicted and a ground-truth normal, each normalised with a floor of 1e-8 on its length
+__device__ __forceinline__ float angular_error_deg(float p0, float p1, float p2, float g0, float g1, float g2) {
+  const float np = fmaxf(sqrtf(p0 * p0 + p1 * p1 + p2 * p2), 1e-8f), ng = fmaxf(sqrtf(g0 * g0 + g1 * g1 + g2 * g2), 1e-8f);
+  const float c = fminf(fmaxf((p0 / np) * (g0 / ng) + (p1 / np) * (g1 / ng) + (p2 / np) * (g2 / ng), -1.f), 1.f);
+  return acosf(c) * 57.29577951308232f;
 }
 
 // pass 1 (scale-invariant only): normal equations of the per-image affine fit
 __global__ __launch_bounds__(256) void dm_fit_partial(const mvp_depth_metrics_args p, double* part) {
-  __shared__ double red[4];
+  __shared__ double red[4][5];
   const int b = blockIdx.y, ch = blockIdx.x;
   const int64_t per = (p.HW + MT_NCH - 1) / MT_NCH, i0 = ch * per, i1 = min(p.HW, i0 + per);
   double s[5] = {0, 0, 0, 0, 0};
@@ -26,9 +31,10 @@ __global__ __launch_bounds__(256) void dm_fit_partial(const mvp_depth_metrics_ar
     const float g = p.gt[(int64_t)b * p.HW + i], q = p.pred[(int64_t)b * p.HW + i];
     if (g > 0.f) { s[0] += (double)q * q; s[1] += q; s[2] += 1.0; s[3] += (double)q * g; s[4] += g; }
   }
-  for (int k = 0; k < 5; ++k) {
-    const double v = blk_sum(s[k], red);
-    if (threadIdx.x == 0) part[((int64_t)b * MT_NCH + ch) * 5 + k] = v;
+  block_sum<5>(s, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) part[((int64_t)b * MT_NCH + ch) * 5 + k] = s[k];
   }
 }
 
@@ -48,7 +54,7 @@ __global__ void dm_fit_final(const mvp_depth_metrics_args p, const double* part)
 }
 
 __global__ __launch_bounds__(256) void dm_partial(const mvp_depth_metrics_args p, double* part) {
-  __shared__ double red[4];
+  __shared__ double red[4][9];
   const int b = blockIdx.y, ch = blockIdx.x;
   const int64_t per = (p.HW + MT_NCH - 1) / MT_NCH, i0 = ch * per, i1 = min(p.HW, i0 + per);
   const float sc = p.scale_invariant ? p.scale_shift[2 * b] : 1.f, sh = p.scale_invariant ? p.scale_shift[2 * b + 1] : 0.f;
@@ -59,14 +65,15 @@ __global__ __launch_bounds__(256) void dm_partial(const mvp_depth_metrics_args p
     if (!(g > 0.f)) continue;
     float q = p.pred[(int64_t)b * p.HW + i];
     if (p.scale_invariant) q = q * sc + sh;
-    const float th = fmaxf(g / fmaxf(q, 1e-9f), q / fmaxf(g, 1e-9f));
-    const float d = g - q;
+    float d;
+    const float th = depth_ratio(g, q, d);
     s[0] += 1.0; s[1] += q; s[2] += (double)q * q; s[3] += g; s[4] += (double)g * g;
     s[5] += th < t1 ? 1.0 : 0.0; s[6] += th < t2 ? 1.0 : 0.0; s[7] += th < t3 ? 1.0 : 0.0; s[8] += (double)d * d;
   }
-  for (int k = 0; k < 9; ++k) {
-    const double v = blk_sum(s[k], red);
-    if (threadIdx.x == 0) part[((int64_t)b * MT_NCH + ch) * 9 + k] = v;
+  block_sum<9>(s, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) part[((int64_t)b * MT_NCH + ch) * 9 + k] = s[k];
   }
 }
 
@@ -89,7 +96,7 @@ __global__ void dm_final(const mvp_depth_metrics_args p, const double* part) {
 }
 
 __global__ __launch_bounds__(256) void sm_partial(const mvp_snorm_metrics_args p, double* part) {
-  __shared__ double red[4];
+  __shared__ double red[4][5];
   const int b = blockIdx.y, ch = blockIdx.x;
   const int64_t per = (p.HW + MT_NCH - 1) / MT_NCH, i0 = ch * per, i1 = min(p.HW, i0 + per);
   double s[5] = {0, 0, 0, 0, 0};
@@ -98,15 +105,13 @@ __global__ __launch_bounds__(256) void sm_partial(const mvp_snorm_metrics_args p
     const float* gt = p.gt + ((int64_t)b * 3) * p.HW + i;
     const float g0 = gt[0], g1 = gt[p.HW], g2 = gt[2 * p.HW];
     if (!(fabsf(g0) + fabsf(g1) + fabsf(g2) > 0.f)) continue;
-    const float p0 = pr[0], p1 = pr[p.HW], p2 = pr[2 * p.HW];
-    const float np = fmaxf(sqrtf(p0 * p0 + p1 * p1 + p2 * p2), 1e-8f), ng = fmaxf(sqrtf(g0 * g0 + g1 * g1 + g2 * g2), 1e-8f);
-    const float c = fminf(fmaxf((p0 / np) * (g0 / ng) + (p1 / np) * (g1 / ng) + (p2 / np) * (g2 / ng), -1.f), 1.f);
-    const float e = acosf(c) * 57.29577951308232f;
+    const float e = angular_error_deg(pr[0], pr[p.HW], pr[2 * p.HW], g0, g1, g2);
     s[0] += 1.0; s[1] += (double)e * e; s[2] += e < p.t1 ? 1.0 : 0.0; s[3] += e < p.t2 ? 1.0 : 0.0; s[4] += e < p.t3 ? 1.0 : 0.0;
   }
-  for (int k = 0; k < 5; ++k) {
-    const double v = blk_sum(s[k], red);
-    if (threadIdx.x == 0) part[((int64_t)b * MT_NCH + ch) * 5 + k] = v;
+  block_sum<5>(s, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) part[((int64_t)b * MT_NCH + ch) * 5 + k] = s[k];
   }
 }
 
@@ -168,10 +173,7 @@ __global__ __launch_bounds__(256) void mb_partial(const mvp_metrics_breakdown_ar
       valid = fabsf(g0) + fabsf(g1) + fabsf(g2) > 0.f;
       if (valid) {
         const float* pr = p.pred + ((int64_t)b * p.Cp) * HW + i;
-        const float p0 = pr[0], p1 = pr[HW], p2 = pr[2 * HW];
-        const float np = fmaxf(sqrtf(p0 * p0 + p1 * p1 + p2 * p2), 1e-8f), ng = fmaxf(sqrtf(g0 * g0 + g1 * g1 + g2 * g2), 1e-8f);
-        const float c = fminf(fmaxf((p0 / np) * (g0 / ng) + (p1 / np) * (g1 / ng) + (p2 / np) * (g2 / ng), -1.f), 1.f);
-        x = acosf(c) * 57.29577951308232f;
+        x = angular_error_deg(pr[0], pr[HW], pr[2 * HW], g0, g1, g2);
         se = x * x;
       }
     } else {
@@ -180,8 +182,9 @@ __global__ __launch_bounds__(256) void mb_partial(const mvp_metrics_breakdown_ar
       if (valid) {
         float q = p.pred[(int64_t)b * HW + i];
         if (p.scale_shift) q = q * sc + sh;
-        x = fmaxf(g / fmaxf(q, 1e-9f), q / fmaxf(g, 1e-9f));
-        se = (g - q) * (g - q);
+        float d;
+        x = depth_ratio(g, q, d);
+        se = d * d;
       }
     }
     const double h1 = x < t1 ? 1.0 : 0.0, h2 = x < t2 ? 1.0 : 0.0, h3 = x < t3 ? 1.0 : 0.0;
@@ -241,7 +244,7 @@ extern "C" int mvp_metrics_breakdown(const mvp_metrics_breakdown_args* a, void* 
   if (a->num_levels <= 0 || a->num_levels > MB_MAX_LEVELS || (a->Cp != 0 && a->Cp < 3)) return MVP_EINVAL;
   if (a->seg && (!a->seg_sums || a->num_ids <= 0 || a->num_ids > 2048)) return MVP_EINVAL;
   const int S = a->seg ? a->num_ids : 0, nb = a->num_levels * 5 + S * 6;
-  if (a->workspace_bytes < mvp_metrics_breakdown_workspace_bytes(a->B, a->num_levels, S) || ((uintptr_t)a->workspace & 7)) return MVP_EINVAL;
+  if (a->workspace_bytes < mvp_metrics_breakdown_workspace_bytes(a->B, a->num_levels, S) || !aligned_to(a->workspace, 8)) return MVP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)a->workspace;
   const size_t lds = (size_t)nb * sizeof(double);

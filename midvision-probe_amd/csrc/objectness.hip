@@ -4,9 +4,9 @@
 //   mvp_bce_loss_fwd_bwd    nn.BCELoss (mean) and its gradient
 //   mvp_binary_counts       TP / FP / FN / TN of a thresholded prediction
 // All three stream their operands once or twice and are bound by memory.  Every floating-point reduction is per-workgroup partials in
-// the caller's workspace, folded in a fixed order (no float atomics): the same inputs give the same bits.  The counts are integers, so
-// their 64-bit atomics are exact in any order.
-#include "mvp_common.h"
+// the caller's workspace, folded in a fixed order (no float atomics; csrc/mvp_reduce.h): the same inputs give the same bits.  The
+// counts are integers, so their 64-bit atomics are exact in any order.
+#include "mvp_reduce.h"
 
 namespace {
 
@@ -32,7 +32,8 @@ __device__ __forceinline__ Wf wf_merge(const Wf a, const Wf b) {
   return r;
 }
 
-// every thread returns the merge of the workgroup's 256 values: butterfly inside a wave (lane 0 is what counts), waves 0..3 in order
+// every thread returns the merge of the workgroup's 256 values, in the order of block_sum (csrc/mvp_reduce.h): butterfly inside a wave
+// (lane 0 is what counts), waves 0..3 in order
 template <int CM>
 __device__ __forceinline__ void block_merge(Wf (&w)[CM], Wf (*red)[CM]) {
 #pragma unroll
@@ -54,24 +55,6 @@ __device__ __forceinline__ void block_merge(Wf (&w)[CM], Wf (*red)[CM]) {
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < CM; ++c) w[c] = wf_merge(wf_merge(red[0][c], red[1][c]), wf_merge(red[2][c], red[3][c]));
-}
-
-// the same for plain sums: N values per thread, one LDS round
-template <int N>
-__device__ __forceinline__ void block_sum_n(double (&v)[N], double (*red)[N]) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) red[threadIdx.x >> 6][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
 }
 
 // Row r of the channels-last map: channels 0..C-1 (padding columns are not used).  V4: ld == 4 and a 16-byte aligned base, one
@@ -288,7 +271,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const mvp_bn_act_arg
       }
     }
   }
-  block_sum_n<2 * CM>(acc, red);
+  block_sum<2 * CM>(acc, red);
   if (threadIdx.x == 0) {
     double* ws = (double*)p.workspace;
 #pragma unroll
@@ -317,7 +300,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const mvp_bn_act_args
 #pragma unroll
     for (int c = 0; c < 2 * CM; ++c) acc[c] = 0.0;
     const double* ws = (const double*)p.workspace;
-    for (int i = threadIdx.x; i < nbs; i += 256) {
+    for (int i = threadIdx.x; i < nbs; i += 256) {  // (not fold_rows<2 * CM>: a row holds 2 C <= 2 CM doubles)
 #pragma unroll
       for (int c = 0; c < CM; ++c) {
         if (c < p.C) {
@@ -326,7 +309,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const mvp_bn_act_args
         }
       }
     }
-    block_sum_n<2 * CM>(acc, red);
+    block_sum<2 * CM>(acc, red);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
 #pragma unroll
       for (int c = 0; c < CM; ++c) {
@@ -409,15 +392,14 @@ __global__ __launch_bounds__(256) void bce_kernel(const mvp_bce_loss_args p) {
       if (p.grad_pred) p.grad_pred[i] = g;
     }
   }
-  block_sum_n<1>(acc, red);
+  block_sum<1>(acc, red);
   if (threadIdx.x == 0) ((double*)p.workspace)[blockIdx.x] = acc[0];
 }
 
 __global__ __launch_bounds__(256) void bce_finalize_kernel(const mvp_bce_loss_args p, const int nb) {
   __shared__ double red[4][1];
-  double acc[1] = {0.0};
-  for (int i = threadIdx.x; i < nb; i += 256) acc[0] += ((const double*)p.workspace)[i];
-  block_sum_n<1>(acc, red);
+  double acc[1];
+  fold_rows<1>((const double*)p.workspace, nb, 1, acc, red);
   if (threadIdx.x == 0) p.loss[0] = (float)(acc[0] / (double)p.N);
 }
 
@@ -448,10 +430,7 @@ __global__ __launch_bounds__(256) void counts_kernel(const mvp_binary_counts_arg
     for (int64_t i = t0; i < p.n; i += stride) count(pr[i], gt[i]);
   }
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c[k] += __shfl_xor(c[k], o, 64);
-  }
+  for (int k = 0; k < 4; ++k) c[k] = wave_sum(c[k]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) red[threadIdx.x >> 6][k] = c[k];
@@ -462,8 +441,6 @@ __global__ __launch_bounds__(256) void counts_kernel(const mvp_binary_counts_arg
     if (s) atomicAdd((unsigned long long*)(p.counts + g * 4 + threadIdx.x), s);  // integers: exact in any order
   }
 }
-
-inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 // rows per workgroup and workgroups: at least 1024 rows each, OB_NB workgroups at most
 inline void bn_partition(int64_t P, int64_t& per, int& nb) {
@@ -515,7 +492,7 @@ extern "C" int mvp_bn_act_fwd(const mvp_bn_act_args* a, void* stream) {
   if (sig && a->training && ((int64_t)a->B * a->HW < 2 || a->n < 2)) return MVP_EINVAL;  // one value per channel has no variance
   if (sig && !a->training && (!a->running_mean || !a->running_var)) return MVP_EINVAL;
   if (sig && ((a->running_mean == nullptr) != (a->running_var == nullptr))) return MVP_EINVAL;
-  bn_dispatch(*a, true, sig && a->training, a->ld == 4 && aligned16(a->x), (hipStream_t)stream);
+  bn_dispatch(*a, true, sig && a->training, a->ld == 4 && aligned_to(a->x, 16), (hipStream_t)stream);
   MVP_LAUNCH_CHECK();
   return MVP_OK;
 }
@@ -524,16 +501,16 @@ extern "C" int mvp_bn_act_bwd(const mvp_bn_act_args* a, void* stream) {
   if (!bn_shape_ok(a) || !a->grad_y) return MVP_EINVAL;
   const bool sig = a->act == ACT_SIGMOID;
   if (!a->grad_x && !(sig && (a->grad_gamma || a->grad_beta))) return MVP_EINVAL;  // nothing to compute
-  bn_dispatch(*a, false, sig, a->ld == 4 && aligned16(a->x) && aligned16(a->grad_x), (hipStream_t)stream);
+  bn_dispatch(*a, false, sig, a->ld == 4 && aligned_to(a->x, 16) && aligned_to(a->grad_x, 16), (hipStream_t)stream);
   MVP_LAUNCH_CHECK();
   return MVP_OK;
 }
 
 extern "C" int mvp_bce_loss_fwd_bwd(const mvp_bce_loss_args* a, void* stream) {
   if (!a || !a->pred || !a->target || !a->loss || !a->workspace || a->N <= 0) return MVP_EINVAL;
-  if (a->workspace_bytes < MVP_BCE_WORKSPACE_BYTES || ((uintptr_t)a->workspace & 7)) return MVP_EINVAL;
+  if (a->workspace_bytes < MVP_BCE_WORKSPACE_BYTES || !aligned_to(a->workspace, 8)) return MVP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  const bool v4 = aligned16(a->pred) && aligned16(a->target) && aligned16(a->grad_pred);
+  const bool v4 = aligned_to(a->pred, 16) && aligned_to(a->target, 16) && aligned_to(a->grad_pred, 16);
   int64_t nb = (a->N + 4095) / 4096;  // 4 x 16 bytes of each operand per thread
   nb = nb < 1 ? 1 : (nb > BCE_NB ? BCE_NB : nb);
   if (v4) hipLaunchKernelGGL(bce_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, *a);
@@ -545,14 +522,14 @@ extern "C" int mvp_bce_loss_fwd_bwd(const mvp_bce_loss_args* a, void* stream) {
 
 extern "C" int mvp_binary_counts(const mvp_binary_counts_args* a, void* stream) {
   if (!a || !a->pred || !a->gt || !a->counts || a->G <= 0 || a->G > 65535 || a->n <= 0) return MVP_EINVAL;
-  if (a->n > ((int64_t)1 << 40) / a->G || ((uintptr_t)a->counts & 7)) return MVP_EINVAL;
+  if (a->n > ((int64_t)1 << 40) / a->G || !aligned_to(a->counts, 8)) return MVP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(a->counts, 0, (size_t)a->G * 4 * sizeof(int64_t), s) != hipSuccess) return MVP_ELAUNCH;
   int64_t nb = (a->n + 4095) / 4096;
   const int64_t cap = a->G >= 1024 ? 1 : 1024 / a->G;  // about 1024 workgroups over all groups
   nb = nb < 1 ? 1 : (nb > cap ? cap : nb);
   // every row of a group must start 16-byte aligned for the vector form
-  const bool v4 = aligned16(a->pred) && aligned16(a->gt) && (a->G == 1 || (a->n & 3) == 0);
+  const bool v4 = aligned_to(a->pred, 16) && aligned_to(a->gt, 16) && (a->G == 1 || (a->n & 3) == 0);
   if (v4) hipLaunchKernelGGL(counts_kernel<true>, dim3((unsigned)nb, (unsigned)a->G), dim3(256), 0, s, *a);
   else hipLaunchKernelGGL(counts_kernel<false>, dim3((unsigned)nb, (unsigned)a->G), dim3(256), 0, s, *a);
   MVP_LAUNCH_CHECK();

@@ -28,11 +28,12 @@
 // elements at a time, with one 16-byte load when ld % 4 == 0 and the bases are 16-byte aligned, with four dword loads otherwise (the
 // same elements in the same order: the bits do not depend on the alignment); two partials per workgroup.
 // Pass 2 (both metrics), one wave per triplet: folds the partial rows in a fixed order (lane j takes rows j, j + 64, ...; then the
-// butterfly), forms both scores with one inlined sequence, rounds each ONCE to fp32 and counts.  No floating-point atomics; the counts
-// are integers, whose 64-bit atomics are exact in any order.  Two calls give the same bits.  Nothing between C * H * W and ld is read.
+// butterfly), forms both scores with one inlined sequence, rounds each ONCE to fp32 and counts.  No floating-point atomics
+// (csrc/mvp_reduce.h has the order of every sum); the counts are integers, whose 64-bit atomics are exact in any order.  Two calls give
+// the same bits.  Nothing between C * H * W and ld is read.
 #include <math.h>
 
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
@@ -86,21 +87,13 @@ inline bool px_partition(int B, int C, int H, int W, int metric, px_params* p) {
   return true;
 }
 
-// sums v over the workgroup in a fixed order; the result is valid in thread 0.  red: [PX_THREADS / 64][2]
-__device__ __forceinline__ void px_block_sum2(double a, double b, double (*red)[2], double* out) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6][0] = a;
-    red[threadIdx.x >> 6][1] = b;
-  }
-  __syncthreads();
+// the workgroup's two sums (left, right) to its partial row
+__device__ __forceinline__ void px_store_partial(double sum_l, double sum_q, double (*red)[2], double* out) {
+  double v[2] = {sum_l, sum_q};
+  block_sum_once<2>(v, red);
   if (threadIdx.x == 0) {
-    out[0] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-    out[1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    out[0] = v[0];
+    out[1] = v[1];
   }
 }
 
@@ -195,7 +188,7 @@ __global__ __launch_bounds__(PX_THREADS) void pixel_ssim_partial_kernel(const px
   const double l0 = ssim_point(m0[0], m0[1], m0[3], m0[4], m0[6]), q0 = ssim_point(m0[0], m0[2], m0[3], m0[5], m0[7]);
   const double l1 = ssim_point(m1[0], m1[1], m1[3], m1[4], m1[6]), q1 = ssim_point(m1[0], m1[2], m1[3], m1[5], m1[7]);
   const double sum_l = (in0 ? l0 : 0.0) + (in1 ? l1 : 0.0), sum_q = (in0 ? q0 : 0.0) + (in1 ? q1 : 0.0);
-  px_block_sum2(sum_l, sum_q, red, p.ws + (size_t)blockIdx.x * 2);
+  px_store_partial(sum_l, sum_q, red, p.ws + (size_t)blockIdx.x * 2);
 }
 
 __device__ __forceinline__ void px_sq(double& acc, float a, float b) {
@@ -243,7 +236,7 @@ __global__ __launch_bounds__(PX_THREADS) void pixel_psnr_partial_kernel(const px
     px_sq(sum_l, a, l[i]);
     px_sq(sum_q, a, q[i]);
   }
-  px_block_sum2(sum_l, sum_q, red, p.ws + (size_t)blockIdx.x * 2);
+  px_store_partial(sum_l, sum_q, red, p.ws + (size_t)blockIdx.x * 2);
 }
 
 // the score of one pair from the sum over C * H * W: the mean of the SSIM map, or 10 log10(1 / mse) (mse = 0: +inf)
@@ -255,32 +248,12 @@ __device__ __forceinline__ float px_score(double sum, double n, int metric) {
 __global__ __launch_bounds__(PX_THREADS) void pixel_finish_kernel(const px_params p) {
   const int b = blockIdx.x * (PX_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= p.B) return;  // whole waves
-  const double* w = p.ws + (size_t)b * p.nblk * 2;
-  double v0 = 0.0, v1 = 0.0;
-  for (int j = lane; j < p.nblk; j += 64) {
-    v0 += w[(size_t)j * 2];
-    v1 += w[(size_t)j * 2 + 1];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    v0 += __shfl_xor(v0, o, 64);
-    v1 += __shfl_xor(v1, o, 64);
-  }
+  double v[2];
+  wave_fold_rows<2>(p.ws + (size_t)b * p.nblk * 2, p.nblk, v);
   if (lane != 0) return;
   const double n = (double)p.n;
-  const float s_l = px_score(v0, n, p.metric), s_r = px_score(v1, n, p.metric);
-  const int pr = s_l > s_r ? 0 : 1;  // on the fp32 values that are written; NaN compares false -> 1, two +inf -> 1
-  p.sim[2 * (size_t)b] = s_l;
-  p.sim[2 * (size_t)b + 1] = s_r;
-  p.pred[b] = pr;
-  if (p.label && p.counts) {
-    const float t = p.label[b];
-    const int slot = t == 1.0f ? (pr ? 0 : 2) : (t == 0.0f ? (pr ? 1 : 3) : -1);  // TP FP FN TN, positive = 1
-    if (slot >= 0) atomicAdd((unsigned long long*)(p.counts + slot), 1ull);  // integers: exact in any order
-  }
+  twoafc_verdict(px_score(v[0], n, p.metric), px_score(v[1], n, p.metric), b, p.sim, p.pred, p.label, p.counts);
 }
-
-inline bool px_aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 }  // namespace
 
@@ -295,10 +268,10 @@ extern "C" int mvp_pixel_score(const mvp_pixel_score_args* a, void* stream) {
   if (a->counts && !a->label) return MVP_EINVAL;
   px_params p;
   if (!px_partition(a->B, a->C, a->H, a->W, a->metric, &p) || a->ld < p.n) return MVP_EINVAL;
-  if (!a->workspace || ((uintptr_t)a->workspace & 7) ||
+  if (!a->workspace || !aligned_to(a->workspace, 8) ||
       a->workspace_bytes < mvp_pixel_score_workspace_bytes(a->B, a->C, a->H, a->W, a->metric))
     return MVP_EINVAL;
-  if ((uintptr_t)a->counts & 7) return MVP_EINVAL;
+  if (!aligned_to(a->counts, 8)) return MVP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   p.ref = a->ref; p.left = a->left; p.right = a->right; p.label = a->label;
   p.sim = a->sim; p.pred = a->pred; p.counts = a->counts; p.ws = (double*)a->workspace;
@@ -308,7 +281,7 @@ extern "C" int mvp_pixel_score(const mvp_pixel_score_args* a, void* stream) {
   if (a->metric == 1) {
     hipLaunchKernelGGL(pixel_ssim_partial_kernel, grid, dim3(PX_THREADS), 0, s, p);
   } else {
-    const bool v4 = (a->ld & 3) == 0 && px_aligned16(a->ref) && px_aligned16(a->left) && px_aligned16(a->right);
+    const bool v4 = (a->ld & 3) == 0 && aligned_to(a->ref, 16) && aligned_to(a->left, 16) && aligned_to(a->right, 16);
     if (v4) hipLaunchKernelGGL(pixel_psnr_partial_kernel<true>, grid, dim3(PX_THREADS), 0, s, p);
     else hipLaunchKernelGGL(pixel_psnr_partial_kernel<false>, grid, dim3(PX_THREADS), 0, s, p);
   }

@@ -4,35 +4,15 @@
 //   mvp_masked_l1_fwd_bwd   sum valid |pred - target| / sum valid, and its gradient
 //   mvp_task_metrics        per image and channel: sum of AbsRel, valid pixels, pixels under three ratio thresholds
 // All three stream their operands once (the loss twice: the count is known only after the first pass) and are bound by memory.
-// Every reduction is per-workgroup fp64 partials in the caller's workspace, folded in a fixed order (no float atomics): the same
-// inputs give the same bits.  Counts are carried in fp64, exact below 2^53.
+// Every reduction is per-workgroup fp64 partials in the caller's workspace, folded in a fixed order (no float atomics;
+// csrc/mvp_reduce.h): the same inputs give the same bits.  Counts are carried in fp64, exact below 2^53.
 // The metric arithmetic reproduces a chain of separately rounded fp32 tensor operations: no contraction anywhere in this file.
 #pragma clang fp contract(off)
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
 constexpr int TK_NB = MVP_TASK_WORKSPACE_BYTES / (5 * 8);  // 1024: partial rows at most (5 fp64 each for the metrics, 2 for the loss)
-
-// every thread returns the sum of the workgroup's 256 values: butterfly inside a wave, waves 0..3 in order
-template <int N>
-__device__ __forceinline__ void tk_block_sum(double (&v)[N], double (*red)[N]) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) red[threadIdx.x >> 6][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
-}
-
-inline bool aligned_to(const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; }
 
 // ----------------------------------------------------------------------------- target + valid mask
 // k / 255 or k / 65535 (correctly rounded), then the task's clamp_to (0, maxx): min(max(x, 0), maxx) / maxx
@@ -160,7 +140,7 @@ __global__ __launch_bounds__(256) void l1_reduce_kernel(const mvp_masked_l1_args
       for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) l1_acc(pr[i], tg[i], vm[i], acc);
     }
   }
-  tk_block_sum<2>(acc, red);
+  block_sum<2>(acc, red);
   if (threadIdx.x == 0) {
     double* ws = (double*)p.workspace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
     ws[0] = acc[0];
@@ -178,13 +158,8 @@ template <bool V4>
 __global__ __launch_bounds__(256) void l1_apply_kernel(const mvp_masked_l1_args p, const int64_t per, const int nb) {
   __shared__ double red[4][2];
   // every workgroup folds the partial rows itself, in the same fixed order: the same count everywhere
-  double acc[2] = {0.0, 0.0};
-  const double* ws = (const double*)p.workspace;
-  for (int i = threadIdx.x; i < nb; i += 256) {
-    acc[0] += ws[2 * i];
-    acc[1] += ws[2 * i + 1];
-  }
-  tk_block_sum<2>(acc, red);
+  double acc[2];
+  fold_rows<2>((const double*)p.workspace, nb, 2, acc, red);
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.loss[0] = (float)(acc[0] / acc[1]);  // no valid pixel: 0 / 0
   if (!p.grad_pred) return;
   const float inv = (float)(1.0 / acc[1]);
@@ -262,7 +237,7 @@ __global__ __launch_bounds__(256) void metrics_kernel(const mvp_task_metrics_arg
   } else {
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) tm_acc<FORM>(pr[i], tg[i], vm[i], p.t1, p.t2, p.t3, acc);
   }
-  tk_block_sum<5>(acc, red);
+  block_sum<5>(acc, red);
   if (threadIdx.x < 5) ((double*)p.workspace)[(row * gridDim.x + blockIdx.x) * 5 + threadIdx.x] = acc[threadIdx.x];
 }
 

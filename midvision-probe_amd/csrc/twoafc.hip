@@ -15,11 +15,12 @@
 // the scale).  The workgroup's five sums go to the workspace, one row per (triplet, chunk).
 // Pass 2, one wave per triplet: folds the chunk rows in a fixed order (lane j takes rows j, j + 64, ...; then the butterfly), forms both
 // similarities with ONE inlined sequence (bitwise-equal left / right give bitwise-equal results), rounds each once to fp32 and counts.
-// No floating-point atomics; the counts are integers, whose 64-bit atomics are exact in any order.  Two calls give the same bits.
+// No floating-point atomics (csrc/mvp_reduce.h has the order of every sum); the counts are integers, whose 64-bit atomics are exact
+// in any order.  Two calls give the same bits.
 // Nothing between C * HW and ld is read.
 #include <math.h>
 
-#include "mvp_common.h"
+#include "mvp_reduce.h"
 
 namespace {
 
@@ -167,19 +168,10 @@ __global__ __launch_bounds__(TA_THREADS) void twoafc_partial_kernel(const ta_par
       acc[4] = fma(sq, sq, acc[4]);
     }
   }
+  block_sum<5>(acc, red);  // (block_sum_once here: 64 VGPRs for 103 in the dword form and 2.6 % slower, profiles/reduce_header_bench.txt)
+  if (threadIdx.x == 0) {
 #pragma unroll
-  for (int j = 0; j < 5; ++j) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) red[threadIdx.x >> 6][j] = acc[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    const int j = threadIdx.x;
-    p.ws[(size_t)blockIdx.x * 5 + j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+    for (int j = 0; j < 5; ++j) p.ws[(size_t)blockIdx.x * 5 + j] = acc[j];
   }
 }
 
@@ -193,33 +185,14 @@ __device__ __forceinline__ float ta_cosine(double dot, double nx2, double nr, do
 __global__ __launch_bounds__(TA_THREADS) void twoafc_finish_kernel(const ta_params p) {
   const int b = blockIdx.x * (TA_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= p.B) return;  // whole waves
-  const double* w = p.ws + (size_t)b * p.nchunks * 5;
-  double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int j = lane; j < p.nchunks; j += 64) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) v[k] += w[(size_t)j * 5 + k];
-  }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-  }
+  double v[5];
+  wave_fold_rows<5>(p.ws + (size_t)b * p.nchunks * 5, p.nchunks, v);
   if (lane != 0) return;
   const double hw = (double)p.HW;
   const double nr = fmax(sqrt(v[2]) / hw, 1e-8);
   const float s_l = ta_cosine(v[0], v[3], nr, hw), s_r = ta_cosine(v[1], v[4], nr, hw);
-  const int pr = s_l > s_r ? 0 : 1;  // on the fp32 values that are written; NaN compares false -> 1
-  p.sim[2 * (size_t)b] = s_l;
-  p.sim[2 * (size_t)b + 1] = s_r;
-  p.pred[b] = pr;
-  if (p.label && p.counts) {
-    const float t = p.label[b];
-    const int slot = t == 1.0f ? (pr ? 0 : 2) : (t == 0.0f ? (pr ? 1 : 3) : -1);  // TP FP FN TN, positive = 1
-    if (slot >= 0) atomicAdd((unsigned long long*)(p.counts + slot), 1ull);  // integers: exact in any order
-  }
+  twoafc_verdict(s_l, s_r, b, p.sim, p.pred, p.label, p.counts);
 }
-
-inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 }  // namespace
 
@@ -234,14 +207,14 @@ extern "C" int mvp_twoafc_score(const mvp_twoafc_args* a, void* stream) {
   if (!a || !a->ref || !a->left || !a->right || !a->sim || !a->pred) return MVP_EINVAL;
   if (a->counts && !a->label) return MVP_EINVAL;
   if (!ta_sizes_ok(a->B, a->C, a->HW) || a->ld < (int64_t)a->C * a->HW) return MVP_EINVAL;
-  if (!a->workspace || ((uintptr_t)a->workspace & 7) || a->workspace_bytes < mvp_twoafc_workspace_bytes(a->B, a->C, a->HW)) return MVP_EINVAL;
-  if ((uintptr_t)a->counts & 7) return MVP_EINVAL;
+  if (!a->workspace || !aligned_to(a->workspace, 8) || a->workspace_bytes < mvp_twoafc_workspace_bytes(a->B, a->C, a->HW)) return MVP_EINVAL;
+  if (!aligned_to(a->counts, 8)) return MVP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   ta_params p;
   p.ref = a->ref; p.left = a->left; p.right = a->right; p.label = a->label;
   p.sim = a->sim; p.pred = a->pred; p.counts = a->counts; p.ws = (double*)a->workspace;
   p.ld = a->ld; p.B = a->B; p.C = a->C; p.HW = a->HW;
-  const bool v4 = (a->HW & 3) == 0 && (a->ld & 3) == 0 && aligned16(a->ref) && aligned16(a->left) && aligned16(a->right);
+  const bool v4 = (a->HW & 3) == 0 && (a->ld & 3) == 0 && aligned_to(a->ref, 16) && aligned_to(a->left, 16) && aligned_to(a->right, 16);
   p.gshift = ta_gshift(a->HW, v4);
   ta_partition(a->C, a->HW, TA_THREADS >> p.gshift, p.cc, p.nchunks);  // never more chunks than the workspace query counted
   if (a->counts && !a->accumulate && hipMemsetAsync(a->counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) return MVP_ELAUNCH;
