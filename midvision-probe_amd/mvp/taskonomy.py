@@ -46,6 +46,11 @@ def resolve_task(task: str) -> Tuple[str, Dict[str, object]]:
     raise ValueError(f"unknown Taskonomy task {task!r} (in scope: {sorted(TASKS) + sorted(ALIASES)})")
 
 
+def kernel_task(task: str) -> str:
+    """The dataset's ``task == "depth"`` reads the key "depth" with depth_euclidean's transform; ``resolve_task("depth")`` itself raises."""
+    return "depth_euclidean" if task == "depth" else task
+
+
 def target_channels(task: str) -> int:
     return int(resolve_task(task)[1]["channels"])
 
@@ -81,7 +86,7 @@ class DeviceTaskTransform:
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceTaskTransform needs a HIP device (no CPU fallback on the product path)")
         mean_std(image_mean)
-        resolve_task("depth_euclidean" if task == "depth" else task)
+        resolve_task(kernel_task(task))
         self.batches, self.task, self.image_mean = prefetcher, task, image_mean
         self._scratch = {}
 
@@ -115,12 +120,12 @@ class DeviceTaskTransform:
         if side is not None:
             # one prefetcher serves every pass: its first copies of this pass reuse the buffers the last launches of the previous pass read
             side.wait_stream(torch.cuda.current_stream())
-        kernel_task = "depth_euclidean" if self.task == "depth" else self.task
+        name = kernel_task(self.task)
         for batch in self.batches:
             rgb = batch["rgb"]
             if not rgb.is_cuda:
                 raise RuntimeError("DeviceTaskTransform takes device batches: wrap the loader in mvp.prefetch.DevicePrefetcher")
-            target, valid = prepare_batch(batch[self.task], batch["mask_valid"], kernel_task)
+            target, valid = prepare_batch(batch[self.task], batch["mask_valid"], name)
             yield {"rgb": self._normalise(rgb.contiguous()), self.task: target, "mask_valid": valid}
 
 
@@ -128,7 +133,7 @@ def predict(probe, feats, task: str, size) -> torch.Tensor:
     """probe -> the target's channels -> bilinear resize to the target (the slice comes first: the unused channels are not resized)."""
     from . import functional as MF
 
-    ct = target_channels("depth_euclidean" if task == "depth" else task)
+    ct = target_channels(kernel_task(task))
     pred = probe(feats)
     if pred.shape[1] < ct:
         raise ValueError(f"the probe has {pred.shape[1]} output channels, task {task!r} needs {ct} (probe.output_dim)")
@@ -136,7 +141,7 @@ def predict(probe, feats, task: str, size) -> torch.Tensor:
 
 
 def metric_keys(task: str):
-    name, _ = resolve_task("depth_euclidean" if task == "depth" else task)
+    name, _ = resolve_task(kernel_task(task))
     if name == "principal_curvature":
         return ["AbsRel"] + [f"δ{t}_{k}" for k in ("k1", "k2") for t in ("1.25", "2.5", "3.75")] + [f"δ{t}_avg" for t in ("1.25", "2.5", "3.75")]
     return ["AbsRel"] + [f"δ_{t}" for t in RESHADING_THRESHOLDS]
@@ -147,7 +152,7 @@ def batch_metrics(pred: torch.Tensor, target: torch.Tensor, valid: torch.Tensor,
     channel at a time through ``evaluate_reshading_absrel_and_delta`` (one launch chain for all channels), the mean over the channels."""
     from evals.utils.metrics import _per_image, evaluate_curvature_absrel, task_metric_sums
 
-    name, _ = resolve_task("depth_euclidean" if task == "depth" else task)
+    name, _ = resolve_task(kernel_task(task))
     if name == "principal_curvature":
         return evaluate_curvature_absrel(pred, target, valid)
     absrel, acc = _per_image(task_metric_sums(pred, target, valid, "reshading", RESHADING_THRESHOLDS).cpu())

@@ -43,88 +43,79 @@ def _finish_pending(optimizer):
         fin()
 
 
-def train_depth_step(model, probe, optimizer, scheduler, loss_fn, images, target, detach_model=True, scale_invariant=False, feats=None):
-    """One iteration of train_depth.py:99-143; returns the loss as a DEVICE scalar (the
-    reference's per-step ``loss.item()`` host sync is left to the caller).  ``feats``: the frozen features of ``images`` when
-    the caller already has them in flight (mvp/pipeline.py); None runs the backbone here."""
+def _begin_step(model, optimizer, images, detach_model, feats):
+    """Steps 1-3 of every probe step: drop the old gradients, get the frozen features (``feats`` when the caller already has them in
+    flight, mvp/pipeline.py; None runs the backbone here), land the previous step's overlapped update.  Returns the features."""
     optimizer.zero_grad()
     if feats is None:
         feats = extract_features(model, images, detach_model)
     _finish_pending(optimizer)
+    return feats
+
+
+def _end_step(probe, optimizer, scheduler, feats, loss_of):
+    """Steps 4-8: ``loss_of`` (probe output -> loss), backward, optimiser, schedule; the loss as a DEVICE scalar (the reference's
+    per-step ``loss.item()`` host sync is left to the caller)."""
+    loss = loss_of(probe(feats))
+    MF.backward(loss)
+    optimizer.step()
+    if scheduler is not None:
+        scheduler.step()
+    return loss.detach()
+
+
+def _depth_loss_of(loss_fn, target, scale_invariant):
+    """The tape path's ``loss_of``; built outside train_depth_step so that its tape-free branch pays for no closure cells."""
+    def loss_of(pred):
+        pred = MF.interpolate(pred, size=target.shape[-2:], mode="bilinear")
+        if scale_invariant:  # train_depth.py:116-118: per-image scale/shift fit (detached) + clamp, one fused kernel each way
+            from evals.utils.metrics import match_scale_and_shift
+
+            pred = match_scale_and_shift(pred, target, clamp=(0.001, 1.0))
+        return loss_fn(pred, target)
+
+    return loss_of
+
+
+def train_depth_step(model, probe, optimizer, scheduler, loss_fn, images, target, detach_model=True, scale_invariant=False, feats=None):
+    """One iteration of train_depth.py:99-143."""
+    feats = _begin_step(model, optimizer, images, detach_model, feats)
     plan = fused_step.plan_for(probe, optimizer, scheduler, loss_fn, feats, target, scale_invariant)
     if plan is not None:  # the benchmarked probe: the same launches without the autograd tape (mvp/fused_step.py)
         return plan.run(feats, target, scheduler)
-    pred = probe(feats)
-    pred = MF.interpolate(pred, size=target.shape[-2:], mode="bilinear")
-    if scale_invariant:  # train_depth.py:116-118: per-image scale/shift fit (detached) + clamp, one fused kernel each way
-        from evals.utils.metrics import match_scale_and_shift
-
-        pred = match_scale_and_shift(pred, target, clamp=(0.001, 1.0))
-    loss = loss_fn(pred, target)
-    MF.backward(loss)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
-    return loss.detach()
+    return _end_step(probe, optimizer, scheduler, feats, _depth_loss_of(loss_fn, target, scale_invariant))
 
 
 def train_snorm_step(model, probe, optimizer, scheduler, images, target, mask, detach_model=True, feats=None):
-    """One iteration of train_snorm.py:93-120 (bicubic upsample, angular loss, UA iff 4 channels).  ``feats`` as in
-    ``train_depth_step``."""
+    """One iteration of train_snorm.py:93-120 (bicubic upsample, angular loss, UA iff 4 channels)."""
     from evals.utils.losses import angular_loss
 
-    optimizer.zero_grad()
-    if feats is None:
-        feats = extract_features(model, images, detach_model)
-    _finish_pending(optimizer)
-    pred = probe(feats)
-    pred = MF.interpolate(pred.contiguous(), size=target.shape[-2:], mode="bicubic")
-    uncertainty = pred.shape[1] > 3
-    loss = angular_loss(pred, target, mask, uncertainty_aware=uncertainty)
-    MF.backward(loss)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
-    return loss.detach()
+    def loss_of(pred):
+        pred = MF.interpolate(pred.contiguous(), size=target.shape[-2:], mode="bicubic")
+        return angular_loss(pred, target, mask, uncertainty_aware=pred.shape[1] > 3)
+
+    return _end_step(probe, optimizer, scheduler, _begin_step(model, optimizer, images, detach_model, feats), loss_of)
 
 
 def train_objectness_step(model, probe, optimizer, scheduler, images, target, detach_model=True, feats=None):
-    """One iteration of train_generic_objectness.py:372-398 (bilinear resize to the mask, nn.BCELoss); returns the loss as a device
-    scalar.  ``target``: the float 0 / 1 mask [B, C, H, W] with the probe's channel count.  ``feats`` as in ``train_depth_step``."""
-    optimizer.zero_grad()
-    if feats is None:
-        feats = extract_features(model, images, detach_model)
-    _finish_pending(optimizer)
-    pred = probe(feats)
-    pred = MF.interpolate(pred, size=target.shape[-2:], mode="bilinear")
-    loss = MF.bce_loss(pred, target)
-    MF.backward(loss)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
-    return loss.detach()
+    """One iteration of train_generic_objectness.py:372-398 (bilinear resize to the mask, nn.BCELoss).  ``target``: the float 0 / 1
+    mask [B, C, H, W] with the probe's channel count."""
+    return _end_step(probe, optimizer, scheduler, _begin_step(model, optimizer, images, detach_model, feats),
+                     lambda pred: MF.bce_loss(MF.interpolate(pred, size=target.shape[-2:], mode="bilinear"), target))
 
 
 def train_taskonomy_step(model, probe, optimizer, scheduler, images, target, valid, detach_model=True, feats=None):
     """One iteration of Taskonomy probing (the reference ships the parts, not the loop: INTEGRATION.md lists the conventions): the
     probe's first C_t channels, C_t the target's, are resized bilinearly to the target and meet it in MaskedL1Loss under ``valid``
-    [B, 1, H, W]; the probe's other channels get a zero gradient.  Returns the loss as a device scalar.  ``feats`` as in
-    ``train_depth_step``."""
-    optimizer.zero_grad()
-    if feats is None:
-        feats = extract_features(model, images, detach_model)
-    _finish_pending(optimizer)
-    pred = probe(feats)
-    ct = target.shape[1]
-    if pred.shape[1] < ct:
-        raise ValueError(f"the probe has {pred.shape[1]} output channels, the target {ct} (probe.output_dim)")
-    pred = MF.interpolate(pred[:, :ct], size=target.shape[-2:], mode="bilinear", align_corners=False)
-    loss = MF.masked_l1_loss(pred, target, valid)
-    MF.backward(loss)
-    optimizer.step()
-    if scheduler is not None:
-        scheduler.step()
-    return loss.detach()
+    [B, 1, H, W]; the probe's other channels get a zero gradient."""
+    def loss_of(pred):
+        ct = target.shape[1]
+        if pred.shape[1] < ct:
+            raise ValueError(f"the probe has {pred.shape[1]} output channels, the target {ct} (probe.output_dim)")
+        pred = MF.interpolate(pred[:, :ct], size=target.shape[-2:], mode="bilinear", align_corners=False)
+        return MF.masked_l1_loss(pred, target, valid)
+
+    return _end_step(probe, optimizer, scheduler, _begin_step(model, optimizer, images, detach_model, feats), loss_of)
 
 
 def _device_batches(loader, dev, keys=("image", "depth", "snorm")):

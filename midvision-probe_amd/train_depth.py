@@ -15,9 +15,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import torch  # noqa: E402
 
-from mvp import checkpoint, config  # noqa: E402
+from mvp import checkpoint, config, trainer  # noqa: E402
 from mvp import dist as mdist  # noqa: E402
-from mvp.optim import FlatAdamW  # noqa: E402
 from mvp.train import train, validate  # noqa: E402
 
 
@@ -37,56 +36,30 @@ def self_launch(world: int, argv) -> int:
 
 
 def main(argv):
+    from evals.datasets import build_loader
     from evals.utils.losses import DepthLoss
-    from evals.utils.optim import cosine_decay_linear_warmup
     from mvp import results
 
     cfg = config.compose("depth_training", argv)
     if int(cfg["system"]["num_gpus"]) > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(int(cfg["system"]["num_gpus"]), argv))
-    if float(cfg["optimizer"].get("model_lr", 0.0)) != 0.0:
-        raise NotImplementedError("optimizer.model_lr != 0 (backbone fine-tuning) is outside the frozen-backbone hot path")
+    trainer.check_config(cfg)
+    loaded_ckpt = trainer.checkpoint_for_eval(cfg)  # train_depth.py:526-535,570: an evaluation run scores the probe of cfg.ckpt_path
+    is_eval = loaded_ckpt is not None
     rank, local, world = mdist.env_setup("nccl")
     cfg["system"]["num_gpus"] = world
     torch.manual_seed(int(cfg["system"]["random_seed"]))  # probe initialisation; rank 0's copy is broadcast by FlatAdamW
     dev = torch.device("cuda", torch.cuda.current_device())
-    from evals.datasets import build_loader
-
     ds = cfg["dataset"]
     loader = build_loader(dict(ds, batch_size=cfg["batch_size"]), "train", cfg["batch_size"], num_gpus=world, num_workers=cfg.get("num_workers", 2),
                           with_snorm=False)
-    train_batches, wrap_valid = loader, (lambda ld: ld)
-    if ds.get("augment_train") or ds.get("raw"):
-        # the reference's get_nyu_transforms(augment=True) on the device, between the H2D prefetcher and the frozen forward; raw loaders
-        # (uint8 pixels) are normalised there too, on the validation side with nothing else
-        from mvp.augment import DeviceAugment
-        from mvp.prefetch import DevicePrefetcher
-
-        aug = dict(image_mean=ds.get("image_mean", "imagenet"), seed=int(cfg["system"]["random_seed"]), rank=rank)
-        train_batches = DeviceAugment(DevicePrefetcher(loader, dev, keys=("image", "depth", "snorm")), augment=bool(ds.get("augment_train")),
-                                      rotateflip=bool(ds.get("rotateflip", False)), **aug)
-        if ds.get("raw"):
-            wrap_valid = lambda ld: DeviceAugment(DevicePrefetcher(ld, dev, keys=("image", "depth", "snorm", "segmentation")), augment=False, **aug)  # noqa: E731
-    model = config.instantiate(cfg["backbone"]).to(dev)
-    probe = config.instantiate(cfg["probe"], feat_dim=model.feat_dim, max_depth=ds["max_depth"]).to(dev)
-    if "vit-mae" in model.checkpoint_name or "sam" in model.checkpoint_name:  # train_depth.py:613-617
-        model.resize_pos_embed(image_size=tuple(ds["image_size"]) if ds.get("raw") else tuple(loader.dataset[0]["image"].shape[-2:]))
-    opt = FlatAdamW([{"params": probe.parameters(), "lr": cfg["optimizer"]["probe_lr"]}], overlap_comm=world > 1)
-    n_ep = cfg["optimizer"]["n_epochs"]
-    sched = torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lambda e: cosine_decay_linear_warmup(
-        e, n_ep * len(loader), cfg["optimizer"]["warmup_epochs"] * len(loader)))
-    hist = []
-    is_eval = bool(cfg.get("is_eval", False))
-    loaded_ckpt = None
-    if is_eval:
-        # train_depth.py:526-535,570: an evaluation run scores the probe of cfg.ckpt_path (probe only: the reference's model line is
-        # commented out); without a checkpoint it would score a randomly initialised probe under the real experiment's CSV columns
-        loaded_ckpt = str(cfg.get("ckpt_path", "") or "").replace("\\$", "$")
-        if not loaded_ckpt:
-            raise SystemExit("is_eval=True needs ckpt_path=<.../ckpt.pth> (refusing to validate a randomly initialised probe)")
-        checkpoint.load_checkpoint(loaded_ckpt, model, probe, load_model=False)
-    else:
-        hist = train(model, probe, train_batches, opt, sched, n_ep, detach_model=True, loss_fn=DepthLoss(), rank=rank, world_size=world)
+    augmented, wrap_valid = trainer.nyu_device_batches(cfg, loader, dev, rank, valid_keys=("image", "depth", "snorm", "segmentation"))
+    model, probe = trainer.build_model_and_probe(cfg, dev, multilayer_default=False, eval_backbone=False, max_depth=ds["max_depth"])
+    trainer.resize_pos_embed_for(model, lambda: ds["image_size"] if ds.get("raw") else loader.dataset[0]["image"].shape[-2:])
+    opt, sched = trainer.build_optimizer(cfg, probe, len(loader), world)
+    trainer.load_for_eval(loaded_ckpt, model, probe, load_model=False)
+    hist = [] if is_eval else train(model, probe, loader if augmented is None else augmented, opt, sched, cfg["optimizer"]["n_epochs"],
+                                    detach_model=True, loss_fn=DepthLoss(), rank=rank, world_size=world)
     opt.finish_pending()
     if rank == 0:
         model.eval(); probe.eval()
@@ -103,8 +76,7 @@ def main(argv):
         print("results ->", results.append_result_csv(results.result_csv_path(cfg["output_dir"], "depth", ds["name"], bool(cfg["backbone"].get("add_norm"))), titles, row))
         if not is_eval:
             print("saved", checkpoint.save_checkpoint(ckpt, cfg, model, probe))
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    trainer.finish(world)
 
 
 if __name__ == "__main__":
